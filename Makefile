@@ -7,7 +7,7 @@ test: build       ## CPU suite: oracle KATs, ABI (incl. the C99 client), distrib
 test-gpu: build   ## parity suite on an MI355X
 	python -m pytest tests -q -m gpu
 bench: build      ## one JSON line (roofline + cpu_baseline)
-	python bench.py
+	python bench.py --full
 profile:          ## rocprofv3 evidence for profiles/ (on the GPU box)
 	bash tools/profile_round.sh r02 && bash tools/prof_c4.sh r02_c4 8
 clean:

@@ -15,7 +15,12 @@ MPC steps/s.  Noise comes from the device Philox streams; inputs are resident in
 dominant kernel's duration with the chip to itself, so it comes from a labelled one-stream pass (mpopis_set_overlap(h, 1)) of the same
 workload right after the timed region; `roofline.frac_default_schedule` is the same formula on the timed region's own (time-shared) launches.
 
-  python bench.py --gpus N --steps K --warmup W      (N>1: launched by torch.distributed.run)
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps and the result line (`metric`, `value`, `unit`,
+`ms_per_step`, ...).  `--full` adds everything else, after the timed region: the repeats of the timed region, the roofline passes, the
+mid-lap states, strong scaling (N > 1), the BASELINE configs C2-C4, the CPU baseline with its agreement checks, and the full record (stderr
+and a detail file).  `--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
+
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]      (N>1: launched by torch.distributed.run)
 """
 import argparse
 import json
@@ -66,13 +71,14 @@ def compact_line(out, detail_path=None):
     rep = out.get("repeats")
     if rep:
         c["repeats"] = {"n": rep.get("n"), "ms_median": _r(rep["ms_per_step"]["median"]), "ms_min": _r(rep["ms_per_step"]["min"]), "ms_max": _r(rep["ms_per_step"]["max"])}
-    c["roofline"] = {"bound": rf.get("bound"), "limiter": rf.get("limiter"), "kernel": rf.get("kernel"), "achieved": _r(rf.get("achieved")), "peak": rf.get("peak"), "unit": rf.get("unit"),
-                     "frac": _r(rf.get("frac")), "traffic": _r(rf.get("traffic")),
-                     **{k: _r(rf.get(k)) for k in ("avg_launch_us", "launches", "rollouts_per_launch", "alg_bytes_per_rollout", "frac_default_schedule", "step_frac",
-                                                   "valu_busy_frac", "kernel_traffic_frac", "fp64_executed_frac")},
-                     "one_stream_ms_per_step": _r((rf.get("one_stream") or {}).get("ms_per_step")),
-                     "issue_frac_of_attainable": _r((rf.get("issue_rate") or {}).get("frac_of_attainable")),
-                     "pmc": "fresh" if "matches" in str(rf.get("pmc_source")) else ("stale" if "STALE" in str(rf.get("pmc_source")) else "none")}
+    if rf:
+        c["roofline"] = {"bound": rf.get("bound"), "limiter": rf.get("limiter"), "kernel": rf.get("kernel"), "achieved": _r(rf.get("achieved")), "peak": rf.get("peak"), "unit": rf.get("unit"),
+                         "frac": _r(rf.get("frac")), "traffic": _r(rf.get("traffic")),
+                         **{k: _r(rf.get(k)) for k in ("avg_launch_us", "launches", "rollouts_per_launch", "alg_bytes_per_rollout", "frac_default_schedule", "step_frac",
+                                                       "valu_busy_frac", "kernel_traffic_frac", "fp64_executed_frac")},
+                         "one_stream_ms_per_step": _r((rf.get("one_stream") or {}).get("ms_per_step")),
+                         "issue_frac_of_attainable": _r((rf.get("issue_rate") or {}).get("frac_of_attainable")),
+                         "pmc": "fresh" if "matches" in str(rf.get("pmc_source")) else ("stale" if "STALE" in str(rf.get("pmc_source")) else "none")}
     kms = out.get("kernel_ms_per_step")
     if kms:
         c["kernel_ms_per_step_one_stream"] = {k: _r(v, 4) for k, v in kms.items()}
@@ -458,6 +464,42 @@ def source_sha(files):
 
 
 PMC_SOURCES = ("mpopis_amd/csrc/kernels_rollout.hip", "mpopis_amd/csrc/car_dynamics.h")     # what profiles/pmc_rollout.json measured
+DUMP_LIMIT = 48 << 20          # bytes of Σ′ over all ranks that --dump-outputs writes in full; beyond it a fixed, seeded sample of the slots
+
+
+def dump_outputs(eng, d, rank, world):
+    """--dump-outputs DIR: what the timed path (mpopis_bench_policy_steps) computed in its last step, read back right after the timed region:
+      U.npy       (B, cs)      float64  the rolled plan pol.U of every resident trial
+      Sigma.npy   (S, cs, cs)  float64  Σ′ the last AIS iteration drew from, for the slots in Sigma_slots.npy (all of them up to DUMP_LIMIT)
+    With N > 1 ranks every rank writes its own files with a _rank<r> suffix.  The inputs are fixed by the arguments (seeds, shapes, step counts),
+    so two builds of the project can be compared file by file."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    B, cs = eng.B, eng.cs
+    sig = eng.get_Sigma()
+    keep = max(1, DUMP_LIMIT // (world * cs * cs * 8))
+    slots = np.arange(B) if B <= keep else np.sort(np.random.default_rng(20240000).choice(B, keep, replace=False))
+    np.save(os.path.join(d, "U%s.npy" % sfx), eng.get_U())
+    np.save(os.path.join(d, "Sigma%s.npy" % sfx), np.ascontiguousarray(sig[slots]))
+    np.save(os.path.join(d, "Sigma_slots%s.npy" % sfx), slots.astype(np.float64))
+
+
+def headline_record(args, B, world, dt, rollouts):
+    """The contract fields of the result line: the timed region of `args.steps` steps took dt seconds (the slowest rank's) and executed
+    `rollouts` rollouts on each rank."""
+    return {
+        "metric": "trajectory rollouts/sec (+ MPC steps/sec), Car-Racing K=4096 H=50",
+        "value": rollouts * world / dt, "unit": "rollouts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "mpc_steps_per_s": B * world * args.steps / dt,
+        "config": {"workload": ("Car-Racing 1-car :μΣaismppi K=4096 H=50 N=10 λ=10 λ_ais=20, %d independent trials per GPU (BASELINE configs[4])" % B) if world == 1 else
+                               ("Car-Racing 1-car :μΣaismppi K=4096 H=50 N=10 λ=10 λ_ais=20, %d independent trials IN TOTAL = %d per GPU x %d GPUs (weak scaling of BASELINE configs[4]; "
+                                "configs[4] as written, 64 trials over all GPUs, is the `strong_scaling` block of --full)" % (B * world, B, world)),
+                   "total_trials": B * world,
+                   "trials_per_gpu": B, "rollouts_per_step": int(B * N_AIS * K), "prewarm_steps": PREWARM_STEPS, "parallelism": ("trials sharded x%d, RCCL gather of summary stats" % world) if world > 1 else "one GPU: all trials resident, no collective"},
+    }
 
 
 def self_launch(n):
@@ -484,12 +526,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)       # (the round driver runs `bench.py --gpus 1 --steps 20 --warmup 5`: same as the defaults)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--trials-per-gpu", type=int, default=TRIALS_PER_GPU)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=100, help="extra repetitions of the timed region (after it), for median / min / max")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C2/C3/C4 block (BASELINE configs[1..3])")
-    ap.add_argument("--quick-configs", action="store_true", help="C2/C3/C4 at one trial and fewer steps only (tests)")
-    ap.add_argument("--no-midlap", action="store_true", help="skip the mid-lap-state variant of the workload (N = 1)")
-    ap.add_argument("--multi-stream", action="store_true", help="(accepted for old command lines; the part-chain schedule is the engine's default now and the one-stream pass always runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and the agreement checks against the CPU oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check everything beyond the headline figure (repeats, roofline passes, mid-lap states, "
+                         "strong scaling, C2/C3/C4, CPU baseline) and write the full record; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy (float64)")
+    ap.add_argument("--repeats", type=int, default=100, help="(--full) extra repetitions of the timed region (after it), for median / min / max")
+    ap.add_argument("--no-configs", action="store_true", help="(--full) skip the C2/C3/C4 block (BASELINE configs[1..3])")
+    ap.add_argument("--quick-configs", action="store_true", help="(--full) C2/C3/C4 at one trial and fewer steps only (tests)")
+    ap.add_argument("--no-midlap", action="store_true", help="(--full) skip the mid-lap-state variant of the workload (N = 1)")
+    ap.add_argument("--multi-stream", action="store_true", help="(accepted for old command lines; the part-chain schedule is the engine's default now and the one-stream pass always runs with --full)")
     # development aids for exercising the N > 1 control flow on a 1-GPU box (never used by the driver): all ranks on cuda:0 over gloo.
     # RCCL refuses two ranks on one device, so this also exercises the fall-back from the ABI gather to torch.distributed's.
     ap.add_argument("--allow-gather-fallback", action="store_true",
@@ -638,8 +684,9 @@ def main():
 
     # Before the W warm-up steps: ~0.3 s of the same work, untimed, so that a fresh box has left its idle power state (clock ramp) and every
     # lazily loaded code object / LDS attribute is in place when the contract's warm-up starts.  Reported as config.prewarm_steps.
-    eng.timing_enable(2)                     # HIP events (rollout kernel only) are used by the passes AFTER the timed region; created here, BEFORE the
-    eng.timing_enable(False)                 # warm-up (16 k hipEventCreate calls take ~0.1 s of host time: with the GPU idle meanwhile the timed
+    if args.full:
+        eng.timing_enable(2)                 # HIP events (rollout kernel only) are used by the --full passes AFTER the timed region; created here, BEFORE the
+        eng.timing_enable(False)             # warm-up (16 k hipEventCreate calls take ~0.1 s of host time: with the GPU idle meanwhile the timed
     eng.bench_policy_steps(PREWARM_STEPS)    # region used to start at a lower clock).  The timed region itself records no events: in the default
     eng.bench_policy_steps(args.warmup)      # schedule (four streams) two records per rollout launch cost ~2 % of the step.
     sync()
@@ -654,6 +701,17 @@ def main():
     if dist is not None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank, world)
+    if not args.full:
+        # a plain run ends here: everything below measures or checks more than the headline figure
+        if rank == 0:
+            print(compact_line({**headline_record(args, B, world, dt, rollouts), "summary_gather": gather_path, "rccl_ranks_seen": rccl_ranks_seen}))
+            sys.stdout.flush()
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # R more repetitions of the same timed region (same bracketing), for the spread: median / min / max over R+1 samples.
     samples = [dt]
     for _ in range(max(0, args.repeats)):
@@ -747,7 +805,6 @@ def main():
 
     if rank == 0:
         total_rollouts = rollouts * world
-        value = total_rollouts / dt
         # roofline of the dominant kernel: from the ONE-STREAM pass (a launch = all trials, nothing else on the GPU while it runs) ...
         r_ms, r_n = tm_one["rollout"]
         r_avg_s = (r_ms / max(r_n, 1)) * 1e-3
@@ -783,16 +840,7 @@ def main():
         med = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
         step_bytes = total_rollouts / world * BYTES_PER_ROLLOUT            # per GPU: algorithmic bytes of the whole path in the timed region
         out = {
-            "metric": "trajectory rollouts/sec (+ MPC steps/sec), Car-Racing K=4096 H=50",
-            "value": value, "unit": "rollouts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "mpc_steps_per_s": B * world * args.steps / dt,
-            "config": {"workload": ("Car-Racing 1-car :μΣaismppi K=4096 H=50 N=10 λ=10 λ_ais=20, %d independent trials per GPU (BASELINE configs[4])" % B) if world == 1 else
-                                   ("Car-Racing 1-car :μΣaismppi K=4096 H=50 N=10 λ=10 λ_ais=20, %d independent trials IN TOTAL = %d per GPU x %d GPUs (weak scaling of BASELINE configs[4]; "
-                                    "configs[4] as written, 64 trials over all GPUs, is the `strong_scaling` block)" % (B * world, B, world)),
-                       "total_trials": B * world,
-                       "trials_per_gpu": B, "rollouts_per_step": int(B * N_AIS * K), "prewarm_steps": PREWARM_STEPS, "parallelism": ("trials sharded x%d, RCCL gather of summary stats" % world) if world > 1 else "one GPU: all trials resident, no collective"},
+            **headline_record(args, B, world, dt, rollouts),
             "repeats": {"n": len(samples), "what": "the timed region repeated back to back (first sample = the contract's timed region = `value`)",
                         "ms_per_step": {"median": med / args.steps * 1e3, "min": srt[0] / args.steps * 1e3, "max": srt[-1] / args.steps * 1e3},
                         "value": {"median": total_rollouts / med, "max": total_rollouts / srt[0], "min": total_rollouts / srt[-1]}},

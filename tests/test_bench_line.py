@@ -94,3 +94,13 @@ def test_compact_line_sheds_blocks_rather_than_growing():
     assert len(line.encode()) <= bench.COMPACT_LIMIT
     d = json.loads(line)
     assert "roofline" in d and "cpu_baseline" in d and "configs" not in d
+
+
+def test_compact_line_of_a_plain_run():
+    """a plain run (no --full) measures the headline only: the contract fields, no roofline or other block"""
+    full = {k: v for k, v in canned().items() if k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                                       "vs_baseline", "dtype", "data", "mpc_steps_per_s", "config", "summary_gather", "rccl_ranks_seen")}
+    d = json.loads(bench.compact_line(full))
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "steps", "warmup"):
+        assert d[k] is not None, k
+    assert not {"roofline", "repeats", "midlap", "configs", "cpu_baseline", "c4", "strong_scaling", "detail"} & set(d)

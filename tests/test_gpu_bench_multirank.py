@@ -30,7 +30,7 @@ def _records(out):
 def test_bench_two_ranks_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--same-gpu", "--no-cpu-baseline", "--repeats", "3"]
+           "--backend", "gloo", "--same-gpu", "--no-cpu-baseline", "--repeats", "3", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     c, d = _records(out)
@@ -60,7 +60,7 @@ def test_bench_self_launches_its_ranks():
     """`python bench.py --gpus 2` WITHOUT a launcher (how the driver starts it): bench.py spawns its two ranks itself."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "2",
-           "--backend", "gloo", "--same-gpu", "--no-cpu-baseline"]
+           "--backend", "gloo", "--same-gpu", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     c, d = _records(out)
@@ -72,7 +72,7 @@ def test_bench_self_launches_its_ranks():
 
 def test_bench_single_gpu_line_has_every_baseline_config():
     """N = 1 line: contract fields, repeats statistics, roofline extras and the C2/C3/C4 block (quick variant: one trial each)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline", "--quick-configs"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline", "--quick-configs", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     c, d = _records(out)
@@ -106,7 +106,7 @@ def test_bench_strict_rccl_fails_instead_of_degrading():
     RCCL communicator, so the run must FAIL (exit 3, reason on stderr, no JSON line) rather than report a number whose gather never went
     through csrc/engine_comm.hip.  With --allow-gather-fallback the same command degrades and labels the line."""
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1"]
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--backend", "gloo", "--same-gpu", "--no-cpu-baseline", "--repeats", "0", "--require-rccl"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--backend", "gloo", "--same-gpu", "--no-cpu-baseline", "--repeats", "0", "--require-rccl", "--full"]
     out = subprocess.run(base + ["--master-port", str(_free_port())] + tail, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode != 0
     assert "RCCL behind the C ABI is required" in out.stderr and not [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -114,3 +114,30 @@ def test_bench_strict_rccl_fails_instead_of_degrading():
     assert out.returncode == 0, out.stderr[-2000:]
     c, d = _records(out)
     assert c["summary_gather_path"].startswith("torch.distributed gather") and c["rccl_ranks_seen"] is None and d["rccl_required"] is False
+
+
+def test_plain_run_prints_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the bench sets up, warms up, times --steps steps and prints ONE line with the contract fields (no stderr record, no extra
+    blocks).  --dump-outputs writes what the timed path computed in its last step; two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]
+        c = json.loads(lines[0])
+        assert c["n_gpus"] == 1 and c["steps"] == 3 and c["warmup"] == 1 and c["unit"] == "rollouts/s" and c["higher_is_better"] is True and c["dtype"] == "f64"
+        assert c["config"]["trials_per_gpu"] == 64 and c["ms_per_step"] > 0
+        assert abs(c["value"] - 64 * 10 * 4096 / (c["ms_per_step"] * 1e-3)) < 1e-5 * c["value"]          # every rollout of the 3 timed steps
+        assert not {"roofline", "repeats", "midlap", "configs", "cpu_baseline", "strong_scaling", "detail"} & set(c)
+        assert not [l for l in out.stderr.splitlines() if l.startswith("BENCH_DETAIL ")]
+        dumps.append({f: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    a, b = dumps
+    assert sorted(a) == ["Sigma.npy", "Sigma_slots.npy", "U.npy"] and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["U.npy"].shape == (64, 100) and a["Sigma.npy"].shape == (64, 100, 100) and list(a["Sigma_slots.npy"]) == list(range(64))
+    for f in a:
+        assert a[f].dtype == np.float64 and np.all(np.isfinite(a[f])) and np.array_equal(a[f], b[f]), f
+    assert np.any(a["U.npy"] != 0) and np.all(np.diagonal(a["Sigma.npy"], axis1=1, axis2=2) > 0)

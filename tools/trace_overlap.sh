@@ -4,7 +4,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/${1:-trace}
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d "$O/prof" -o tr -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$O/prof.log" 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$O/prof" -o tr -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --full > "$O/prof.log" 2>&1
 ls -la "$O/prof"
 python - "$O/prof/tr_kernel_trace.csv" <<'PY'
 import csv, sys
