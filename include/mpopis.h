@@ -45,7 +45,9 @@ extern "C" {
  *    handle's shape instead of one stream, and on = 1 means "one stream" instead of "two halves".  Results never depended on the knob (bit-identical
  *    per slot in every schedule), so a version-3 caller sees the same numbers, sooner.
  * 5: + mpopis_comm_count (the number of ranks RCCL itself reports for the handle's communicator).  Limits lifted, nothing changed in meaning: any K for
- *    :cemppi / :cmamppi / :pmcmppi (were <= 8192 / 7168), and cond(Σ) beyond 1e14 under :cmamppi is computed instead of MPOPIS_ERR_NUMERIC. */
+ *    :cemppi / :cmamppi / :pmcmppi (were <= 8192 / 7168), and cond(Σ) beyond 1e14 under :cmamppi is computed instead of MPOPIS_ERR_NUMERIC.
+ *    Later gained the enum value MPOPIS_POL_NESMPPI = 8 and nothing else (no entry point, mpopis_config unchanged): a library without it answers
+ *    policy = 8 with MPOPIS_ERR_ARG / "No policy_type of that kind", which is how a caller detects support. */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -63,7 +65,9 @@ enum { MPOPIS_POL_MPPI = 0,            /* :mppi       MPPI_Policy      :107-216 
        MPOPIS_POL_CMAMPPI = 4,         /* :cmamppi    CMAMPPI_Policy   :478-606 */
        MPOPIS_POL_MUAISMPPI = 5,       /* :μaismppi   μAISMPPI_Policy  :612-671 */
        MPOPIS_POL_MUSIGMAAISMPPI = 6,  /* :μΣaismppi  μΣAISMPPI_Policy :677-742 */
-       MPOPIS_POL_PMCMPPI = 7 };       /* :pmcmppi    PMCMPPI_Policy   :748-817 */
+       MPOPIS_POL_PMCMPPI = 7,         /* :pmcmppi    PMCMPPI_Policy   :748-817 */
+       MPOPIS_POL_NESMPPI = 8 };       /* :nesmppi    NESMPPI_Policy   :819-893 (exported, src/MPOPIS.jl:34; not a get_policy symbol)
+                                        *   opt_its in ais_its, step_factor in cma_sigma; K >= 2, cs <= 512 */
 
 enum { MPOPIS_SIGMA_EST_MLE = 0, MPOPIS_SIGMA_EST_SS = 1, MPOPIS_SIGMA_EST_LW = 2, MPOPIS_SIGMA_EST_RBLW = 3,
        MPOPIS_SIGMA_EST_OAS = 4 };   /* CEMPPI Σ_est :414-426 (:mle exact; shrinkage estimators restate CovarianceEstimation.jl, unpinned) */
@@ -95,7 +99,7 @@ typedef struct {
     double alpha;              /* α ; γ = λ(1-α)                                                  */
     double lambda_ais;         /* λ_ais (:μaismppi/:μΣaismppi/:pmcmppi)                           */
     double elite_threshold;    /* ce_elite_threshold / elite_perc_threshold                       */
-    double cma_sigma;          /* σ (:cmamppi)                                                    */
+    double cma_sigma;          /* σ (:cmamppi) / step_factor (:nesmppi)                           */
     uint64_t seed;             /* trial slot b draws from seed+b+1 (seed!(pol, seed+k), car_example.jl:188) */
 } mpopis_config;
 
@@ -139,7 +143,7 @@ int  mpopis_seed(mpopis_handle *h, uint64_t seed);                          /* s
 int  mpopis_seed_slots(mpopis_handle *h, const uint64_t *seeds /* B */);
 /* Σ′ of the proposal MvNormal the LAST executed AIS iteration of the last policy step drew from, per slot:
  * B x (cs x cs col-major).  (:447,:723,:796 `P = MvNormal(Σ′)`; :cmamppi with N > 1: σ²·Σ′, :550-554; policies
- * that keep pol.Σ fixed return pol.Σ.)  Lets a caller compare the adapted covariance, which the reference
+ * that keep pol.Σ fixed return pol.Σ; :nesmppi: A′'A′ of the last executed iteration, pol.Σ when the call broke at n = 1.)  Lets a caller compare the adapted covariance, which the reference
  * only exposes indirectly through the next draw. */
 int  mpopis_get_Sigma(mpopis_handle *h, double *Sigma_out /* B*cs*cs */);
 

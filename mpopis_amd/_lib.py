@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("MPOPIS_HIP_LIB") or os.path.join(_HERE, "lib", "libmp
 ENV_MOUNTAINCAR, ENV_CAR, ENV_CARTPOLE = 0, 1, 2
 ENV_IDS = {"mountaincar": ENV_MOUNTAINCAR, "car": ENV_CAR, "cartpole": ENV_CARTPOLE}
 POLICY_IDS = {"mppi": 0, "gmppi": 1, "imppi": 2, "cemppi": 3, "cmamppi": 4,
-              "μaismppi": 5, "muaismppi": 5, "μΣaismppi": 6, "musigmaaismppi": 6, "pmcmppi": 7}
+              "μaismppi": 5, "muaismppi": 5, "μΣaismppi": 6, "musigmaaismppi": 6, "pmcmppi": 7,
+              "nesmppi": 8}
 SIGMA_EST_IDS = {"mle": 0, "ss": 1, "lw": 2, "rblw": 3, "oas": 4}
 ERR_ARG, ERR_NOT_PD, ERR_ACTION, ERR_HIP, ERR_NUMERIC = -1, -2, -3, -4, -5
 RECORD_LEN = 16

@@ -178,6 +178,16 @@ void launch_potrf(const double* A, size_t Astride, double* L, int B, int n, cons
 void launch_chol_solve_gvec(const double* L, size_t Lstride, const double* Uorig, double gamma, double* g, int B, int n, const int* active, hipStream_t s,
                             const double* inv_scale2 = nullptr);      // L = chol(Σ) while the proposal is MvNormal(s²Σ) (:cmamppi): g = (s²Σ)^-1 γU = Σ^-1 γU / s²
 void launch_gvec_from_inv(const double* Sinv, const double* Uorig, double gamma, double* g, int B, int n, hipStream_t s);
+// :nesmppi (kernels_nes.hip; kernels_invsqrt.hip for the square root)
+void launch_nes_break(const double* cost, int B, int K, int* active, int* status, hipStream_t s);
+size_t nes_scatter_workspace_doubles(int B, int cs, int ksplit);
+void launch_nes_scatter(const double* E, const double* cost, double* part, double* M, double* g, double* Csum, int B, int cs, int K, int ksplit,
+                        const int* active, hipStream_t s);
+void launch_nes_potri(const double* L, size_t Lstride, double* X, double* S, int B, int n, const int* active, hipStream_t s);
+void launch_nes_update(const double* E, const double* cost, double* part, int ksplit, const double* S, size_t Sstride, double* M, double* T,
+                       double* g, double* Csum, const double* Ain, size_t Astride, double* Aout, double* Sig, double* U,
+                       int B, int cs, int K, double step_factor, const int* active, hipStream_t s);
+void launch_sym_sqrt(const double* A, double* M, double* V, double* out, int* status, int n, hipStream_t s);
 // kernels_mfma.hip
 void launch_trmm_LZ_mfma(const double* L, size_t Lstride, const double* Z, double* E, int B, int n, int K, const int* active, hipStream_t s,
                          const double* oscale2 = nullptr);      // oscale2[b] (nullable): E = sqrt(oscale2[b]) L Z

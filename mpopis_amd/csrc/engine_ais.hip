@@ -4,6 +4,7 @@
 //   :pmcmppi             multinomial resampling via alias table, moments of E[:,idx]   :802-809
 //   :cemppi              elite selection, early break, Σ′ = cov(est, elite') + 10e-9 I  :453-466
 //   :cmamppi             CMA-ES style path/σ/Σ adaptation (with the reference's quirks) :561-600
+//   :nesmppi             natural-gradient step on (U, A′), Σ′ = A′'A′ (kernels_nes.hip)  :866-878
 #include "engine.h"
 #include "engine_handle.h"
 
@@ -171,6 +172,23 @@ int mpopis_handle::ais_update(int n, bool injected) {
                                lan_regions, lan_coop());
         launch_cma_paths(d_Cdw, d_fro, d_E, d_order, d_cma_ws, d_Ucur, d_cma_scal, d_cma_vec, d_sig2, B, cs, K, n, cma_consts, m_elite, d_active, stream);
         launch_cma_sigma_update(d_Sig, d_cma_scal, d_cma_vec, B, cs, cma_consts, m_elite, d_active, stream);
+        time_end();
+        return MPOPIS_OK;
+    }
+    if (pol == MPOPIS_POL_NESMPPI) {                                                           // :868-878
+        time_begin(5);
+        launch_nes_break(d_cost, B, K, d_active, d_status, stream);                          // early break :868-870 clears active[b]
+        time_end();
+        time_begin(4);
+        const size_t nn = (size_t)cs * cs;
+        // Σ^-1 = invcov(MvNormal(Σ′)) of THIS iteration: Σ0^-1 (formed at mpopis_set_Sigma) at n = 1, else from the factor it sampled from
+        const double* S = d_nesS0; size_t Sstride = 0;
+        if (n > 1) { launch_nes_potri(d_L, nn, d_tmpS, d_nesS, B, cs, d_active, stream); S = d_nesS; Sstride = nn; }
+        // A′: pol.A (shared) into the first buffer at n = 1, then ping-pong (never in place)
+        const double* Ain = (n == 1) ? d_nesA0 : d_nesA[n & 1];
+        double* Aout = d_nesA[(n - 1) & 1];
+        launch_nes_update(d_E, d_cost, d_nespart, ksplit, S, Sstride, d_nesM, d_tmpS, d_nesg, d_nesC, Ain, n == 1 ? 0 : nn, Aout, d_Sig, d_Ucur,
+                          B, cs, K, cfg.cma_sigma, d_active, stream);
         time_end();
         return MPOPIS_OK;
     }

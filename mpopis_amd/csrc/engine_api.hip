@@ -178,8 +178,14 @@ int mpopis_create(const mpopis_config* cfg, mpopis_handle** out) {
     const bool car = cfg->env_kind == MPOPIS_ENV_CAR;
     if (!(car || cfg->env_kind == MPOPIS_ENV_MOUNTAINCAR || cfg->env_kind == MPOPIS_ENV_CARTPOLE)) { g_create_error = "unknown env kind"; return MPOPIS_ERR_ARG; }
     if (car && (cfg->num_cars < 1 || cfg->num_cars > kMaxCars)) { g_create_error = "num_cars must be 1..4"; return MPOPIS_ERR_ARG; }
-    if (cfg->policy < MPOPIS_POL_MPPI || cfg->policy > MPOPIS_POL_PMCMPPI) { g_create_error = "No policy_type of that kind"; return MPOPIS_ERR_ARG; }
+    if (cfg->policy < MPOPIS_POL_MPPI || cfg->policy > MPOPIS_POL_NESMPPI) { g_create_error = "No policy_type of that kind"; return MPOPIS_ERR_ARG; }
     if (cfg->num_samples < 1 || cfg->horizon < 1 || cfg->batch < 1) { g_create_error = "num_samples, horizon, batch must be >= 1"; return MPOPIS_ERR_ARG; }
+    if (cfg->policy == MPOPIS_POL_NESMPPI) {
+        // K = 1: maximum(abs.(diff(cost))) of an empty diff throws in the reference (src/mppi_mpopi_policies.jl:868)
+        if (cfg->num_samples < 2) { g_create_error = "nesmppi: num_samples must be >= 2 (the early-break test takes diff(cost))"; return MPOPIS_ERR_ARG; }
+        if ((car ? 2 * cfg->num_cars : 1) * cfg->horizon > 512) { g_create_error = "nesmppi: control space too large (cs <= 512, the range of the dense Σ′ scatter)"; return MPOPIS_ERR_ARG; }
+        if (!std::isfinite(cfg->cma_sigma)) { g_create_error = "nesmppi: step_factor (cma_sigma) must be finite"; return MPOPIS_ERR_ARG; }
+    }
     if (cfg->policy == MPOPIS_POL_CMAMPPI && (car ? 2 * cfg->num_cars : 1) * cfg->horizon > invsqrt_max_n()) { g_create_error = "cmamppi: control space too large for the on-chip Σ^-0.5 δw kernel"; return MPOPIS_ERR_ARG; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available (the engine has no CPU fallback)"; return MPOPIS_ERR_HIP; }
@@ -255,6 +261,11 @@ int mpopis_create(const mpopis_config* cfg, mpopis_handle** out) {
         h->lan_regions = invsqrt_coop_groups(B, cs);
         rc |= dalloc(h, &h->d_lanV, invsqrt_workspace_doubles(B, cs, h->lan_regions)); rc |= dalloc(h, &h->d_lan_x, invsqrt_coop_words(B, cs)); rc |= dalloc(h, &h->d_Cdw, (size_t)B * cs);
         rc |= dalloc(h, &h->d_fro_part, (size_t)B * ((cs + 15) / 16)); rc |= dalloc(h, &h->d_tri_dinv, trtri_dinv_doubles(B, cs)); rc |= dalloc(h, &h->d_fro, B); rc |= dalloc(h, &h->d_lan_m, B); rc |= dalloc(h, &h->d_lan_prep, lanczos_prep_doubles(B)); rc |= dalloc(h, &h->d_tri_cnt, 2 * (size_t)B);
+    }
+    if (cfg->policy == MPOPIS_POL_NESMPPI) {
+        rc |= dalloc(h, &h->d_nesA0, nn); rc |= dalloc(h, &h->d_nesS0, nn); rc |= dalloc(h, &h->d_nesS, (size_t)B * nn);
+        rc |= dalloc(h, &h->d_nesA[0], (size_t)B * nn); rc |= dalloc(h, &h->d_nesA[1], (size_t)B * nn); rc |= dalloc(h, &h->d_nesM, (size_t)B * nn);
+        rc |= dalloc(h, &h->d_nesg, (size_t)B * cs); rc |= dalloc(h, &h->d_nesC, B); rc |= dalloc(h, &h->d_nespart, nes_scatter_workspace_doubles(B, cs, h->ksplit));
     }
     if (cfg->log_trajectories) rc |= dalloc(h, &h->d_traj, (size_t)B * K * h->T * h->ss);
     if (rc) { g_create_error = h->err; mpopis_destroy(h); return MPOPIS_ERR_HIP; }
@@ -440,6 +451,22 @@ int mpopis_set_Sigma(mpopis_handle* h, const double* Sigma, int32_t n) {
     HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, wait_stream(h->stream));
     if (h->h_status[0] != 0) { h->err = "PosDefException: Sigma is not positive definite"; return MPOPIS_ERR_NOT_PD; }
+    if (h->cfg.policy == MPOPIS_POL_NESMPPI) {
+        // pol.A = sqrt(pol.Σ) (src/mppi_mpopi_policies.jl:849) and the first iteration's invcov(MvNormal(pol.Σ)) = L0^-T L0^-1, once per pol.Σ.
+        // Diagonal: closed form; otherwise the device's symmetric eigen-solve (d_tmpS / d_nesM are scratch outside a policy step)
+        if (diag) {
+            std::vector<double> a0((size_t)cs * cs, 0.0);
+            for (int i = 0; i < cs; ++i) a0[(size_t)i * (cs + 1)] = ds[i];
+            HIPCHK(h, hipMemcpyAsync(h->d_nesA0, a0.data(), sizeof(double) * cs * cs, hipMemcpyHostToDevice, h->stream));
+        } else {
+            launch_sym_sqrt(h->d_Sigma0, h->d_tmpS, h->d_nesM, h->d_nesA0, h->d_status, cs, h->stream);
+        }
+        launch_nes_potri(h->d_L0, 0, h->d_tmpS, h->d_nesS0, 1, cs, nullptr, h->stream);
+        HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, wait_stream(h->stream));
+        HIPCHK(h, hipGetLastError());
+        if (h->h_status[0] != 0) { h->err = "PosDefException: sqrt(Sigma) has a non-positive eigenvalue"; return MPOPIS_ERR_NOT_PD; }
+    }
     return MPOPIS_OK;
 }
 
@@ -780,6 +807,7 @@ void mpopis_handle::shift_slots(ptrdiff_t db) {
     mv(d_cma_scal, 8); mv(d_cma_vec, 3 * (ptrdiff_t)cs); mv(d_sig2, 1);
     mv(d_lanV, (ptrdiff_t)invsqrt_workspace_doubles(1, cs, lan_regions)); mv(d_lan_x, (ptrdiff_t)invsqrt_coop_words(1, cs)); mv(d_Cdw, cs); mv(d_fro_part, (cs + 15) / 16); mv(d_tri_dinv, (ptrdiff_t)trtri_dinv_doubles(1, cs)); mv(d_fro, 1); mv(d_lan_m, 1); mv(d_lan_prep, (ptrdiff_t)lanczos_prep_doubles(1)); mv(d_tri_cnt, 2);
     mv(d_coop_flags, (ptrdiff_t)potrf_coop_flag_words(1, cs)); mv(d_potrf_redo, 1); mv(d_lan_redo, 1);
+    mv(d_nesS, nn); mv(d_nesA[0], nn); mv(d_nesA[1], nn); mv(d_nesM, nn); mv(d_nesg, cs); mv(d_nesC, 1); mv(d_nespart, (ptrdiff_t)nes_scatter_workspace_doubles(1, cs, ksplit));
     mv(alive_gate, 1);
 }
 

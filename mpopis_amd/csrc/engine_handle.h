@@ -65,6 +65,8 @@ struct mpopis_handle {
     int* d_alias_need = nullptr;                                                           // :pmcmppi: slots whose alias table the parallel construction could not certify
     int* d_lan_m = nullptr;                                                                // Lanczos steps taken per slot (diagnostic)
     unsigned long long* d_tri_cnt = nullptr;                                               // [B][2]: arrival counter of a slot's trace workgroups (the last one prepares the Lanczos run) and their ||Σ||_inf; zero between launches
+    // :nesmppi: A0 = sqrt(pol.Σ) and Σ0^-1 (shared, formed at mpopis_set_Sigma); per slot Σ^-1 of the iteration, A′ (ping-pong), M / G, the scatter's g, C, partials
+    double *d_nesA0 = nullptr, *d_nesS0 = nullptr, *d_nesS = nullptr, *d_nesA[2] = {nullptr, nullptr}, *d_nesM = nullptr, *d_nesg = nullptr, *d_nesC = nullptr, *d_nespart = nullptr;
     double *d_qdist = nullptr, *d_qbeta = nullptr; int* d_qwithin = nullptr;
     // Level-3 harness
     double* d_hs = nullptr; int* d_alive = nullptr; const int* alive_gate = nullptr; bool status_sticky = false;

@@ -323,15 +323,14 @@ __host__ __device__ inline size_t invsqrt_slot_doubles(int n, int Gs) {
 // round-robin order (n/2 disjoint rotations per round: phase 1 the angles, phase 2 the column rotations of M and V, phase 3 the row rotations of M) instead of
 // the row-cyclic one.  Stops like the oracle (off-diagonal mass <= 1e-30 of the diagonal's, at most 60 sweeps).  Then y = V diag(λ^-1/2) V' b, fro = sum 1/λ;
 // a non-positive eigenvalue is the reference's DomainError / the oracle's -2 (MPOPIS_ERR_NOT_PD).  ~0.1 s per call at n = 300: a cold path, not a fast one.
-__device__ __noinline__ void dense_invsqrt_slot(const double* __restrict__ A, const double* __restrict__ bv, double* M, double* V, double* __restrict__ y,
-                                                double* __restrict__ fro_out, int* __restrict__ status_b, int n, double* sh /* >= 3 n + 40 doubles of LDS */) {
+// The Jacobi iteration alone: M <- V' A V (diagonal on return, up to the stopping rule), V accumulated.  (Shared with k_sym_sqrt below.)
+__device__ __noinline__ void jacobi_eig_slot(const double* __restrict__ A, double* M, double* V, int n, double* sh /* >= 3 n + 40 doubles of LDS */) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, NT = kLanThreads;
     const int ne = (n + 1) & ~1, np = ne / 2;
     double* Cc = sh;                       // [np]
     double* Ss = Cc + np;                  // [np]
     int* Pq = reinterpret_cast<int*>(Ss + np);      // [2 np] ints
     double* red = Ss + np + np + 2;        // [2 * kLanWaves]
-    double* ev = red + 2 * kLanWaves;      // [n]  (ev, then t = V' b scaled)
     for (int e = tid; e < n * n; e += NT) { M[e] = A[e]; V[e] = (e / n == e % n) ? 1.0 : 0.0; }
     __syncthreads();
     for (int sweep = 0; sweep < 60; ++sweep) {
@@ -386,6 +385,16 @@ __device__ __noinline__ void dense_invsqrt_slot(const double* __restrict__ A, co
             __syncthreads();
         }
     }
+}
+
+__device__ __noinline__ void dense_invsqrt_slot(const double* __restrict__ A, const double* __restrict__ bv, double* M, double* V, double* __restrict__ y,
+                                                double* __restrict__ fro_out, int* __restrict__ status_b, int n, double* sh /* >= 3 n + 40 doubles of LDS */) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, NT = kLanThreads;
+    const int ne = (n + 1) & ~1, np = ne / 2;
+    double* red = sh + np + np + np + 2;   // [2 * kLanWaves]  (the layout of jacobi_eig_slot)
+    double* ev = red + 2 * kLanWaves;      // [n]  (ev, then t = V' b scaled)
+    jacobi_eig_slot(A, M, V, n, sh);
+    __syncthreads();
     // ---- eigenvalues, y = V diag(λ^-1/2) V' b, fro = sum 1/λ
     int bad = 0;
     double fr = 0.0;
@@ -777,6 +786,34 @@ void launch_lanczos_invsqrt(const double* A, const double* prep, const double* b
     ensure_dyn_lds((const void*)k_lanczos_invsqrt<false>, 150 * 1024, seen2);
     hipLaunchKernelGGL(k_lanczos_invsqrt<false>, dim3(B), dim3(kLanThreads), lds1, s, A, bvec, bstride, prep, V, y, fro, msteps, n, nvl1, nvl1,
                        status, active, 1, regions_per_slot, (unsigned long long*)nullptr, 0ull, (int*)nullptr, 0ull, 0);
+}
+
+// :nesmppi's A = sqrt(Σ) of a dense pol.Σ (src/mppi_mpopi_policies.jl:849, LinearAlgebra's sqrt of a symmetric matrix: eigen-based): the Jacobi
+// iteration above on ONE workgroup, then A = V diag(λ^½) V', lower triangle computed and mirrored.  A non-positive eigenvalue is MPOPIS_ERR_NOT_PD
+// (the reference's MvNormal(Σ) would throw PosDefException).  Once per mpopis_set_Sigma; M, V: n x n global scratch.
+__global__ void __launch_bounds__(kLanThreads) k_sym_sqrt(const double* __restrict__ A, double* M, double* V, double* __restrict__ out, int* status, int n) {
+    extern __shared__ __attribute__((aligned(16))) double sh_sq[];
+    jacobi_eig_slot(A, M, V, n, sh_sq);
+    __syncthreads();
+    double* ev = sh_sq;                    // [n] (the rotation scratch is free now)
+    int bad = 0;
+    for (int j = threadIdx.x; j < n; j += kLanThreads) { const double l = M[j + (size_t)j * n]; if (!(l > 0.0)) bad = 1; ev[j] = l > 0.0 ? sqrt(l) : 0.0; }
+    bad = __syncthreads_or(bad);
+    if (bad) { if (threadIdx.x == 0) status_raise(status, MPOPIS_ERR_NOT_PD); return; }
+    for (int e = threadIdx.x; e < n * n; e += kLanThreads) {
+        const int i = e % n, j = e / n;
+        if (i < j) continue;
+        double s = 0.0;
+        for (int m = 0; m < n; ++m) s = fma(V[i + (size_t)m * n] * ev[m], V[j + (size_t)m * n], s);
+        out[i + (size_t)j * n] = s;
+        out[j + (size_t)i * n] = s;
+    }
+}
+void launch_sym_sqrt(const double* A, double* M, double* V, double* out, int* status, int n, hipStream_t s) {
+    const size_t lds = (size_t)(3 * ((n + 1) / 2) + 2 + 2 * kLanWaves + n + 8) * sizeof(double);
+    static std::atomic<unsigned long long> seen{0};
+    ensure_dyn_lds((const void*)k_sym_sqrt, 64 * 1024, seen);
+    hipLaunchKernelGGL(k_sym_sqrt, dim3(1), dim3(kLanThreads), lds, s, A, M, V, out, status, n);
 }
 
 }  // namespace mpopis

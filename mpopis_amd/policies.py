@@ -183,6 +183,16 @@ class PMCMPPI_Policy(AbstractGMPPI_Policy):
         self.opt_its, self.λ_ais = opt_its, λ_ais
 
 
+class NESMPPI_Policy(AbstractGMPPI_Policy):
+    """Natural-evolution-strategy MPOPI, src/mppi_mpopi_policies.jl:819-893 (exported, src/MPOPIS.jl:34; no get_policy symbol).
+    pol.A = sqrt(pol.Σ) lives on the device (formed when Σ is set)."""
+    _kind = "nesmppi"
+
+    def __init__(self, env, opt_its=10, step_factor=0.01, **kw):
+        super().__init__(env, _extra=dict(ais_its=opt_its, step_factor=step_factor), **kw)
+        self.opt_its, self.step_factor = opt_its, step_factor
+
+
 # ASCII aliases
 muAISMPPI_Policy = μAISMPPI_Policy
 muSigmaAISMPPI_Policy = μΣAISMPPI_Policy
