@@ -47,7 +47,10 @@ extern "C" {
  * 5: + mpopis_comm_count (the number of ranks RCCL itself reports for the handle's communicator).  Limits lifted, nothing changed in meaning: any K for
  *    :cemppi / :cmamppi / :pmcmppi (were <= 8192 / 7168), and cond(Σ) beyond 1e14 under :cmamppi is computed instead of MPOPIS_ERR_NUMERIC.
  *    Later gained the enum value MPOPIS_POL_NESMPPI = 8 and nothing else (no entry point, mpopis_config unchanged): a library without it answers
- *    policy = 8 with MPOPIS_ERR_ARG / "No policy_type of that kind", which is how a caller detects support. */
+ *    policy = 8 with MPOPIS_ERR_ARG / "No policy_type of that kind", which is how a caller detects support.
+ *    Later still, num_cars up to MPOPIS_MAX_CARS = 8 (was 4), and nothing else: a library that predates it answers num_cars = 5..8 with
+ *    MPOPIS_ERR_ARG / "num_cars must be 1..4".  Since then :cemppi, :μΣaismppi and :pmcmppi refuse cs > 800 at create (MPOPIS_ERR_ARG): their
+ *    covariance scatter stages at most 800 rows, and earlier libraries returned a wrong Σ′ there (past 512 rows) instead of refusing. */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -56,6 +59,8 @@ enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_AC
  * CarRacingEnv src/envs/car_racing.jl (num_cars==1) / MultiCarRacingEnv src/envs/multi-car_racing.jl;
  * RL.jl CartPoleEnv(continuous=true) + src/examples/cartpole_example.jl:3-6 (state [x,xdot,theta,thetadot]) */
 enum { MPOPIS_ENV_MOUNTAINCAR = 0, MPOPIS_ENV_CAR = 1, MPOPIS_ENV_CARTPOLE = 2 };
+/* largest num_cars of the car env (MultiCarRacingEnv(N) takes any N in the reference) */
+#define MPOPIS_MAX_CARS 8
 
 /* policy kinds = get_policy symbols, src/examples/example_utils.jl:20-128 */
 enum { MPOPIS_POL_MPPI = 0,            /* :mppi       MPPI_Policy      :107-216 */
@@ -87,7 +92,9 @@ typedef struct mpopis_handle mpopis_handle;
 typedef struct {
     int32_t device;            /* HIP device ordinal                                              */
     int32_t env_kind;          /* MPOPIS_ENV_*                                                    */
-    int32_t num_cars;          /* car env: 1 => CarRacingEnv, >1 => MultiCarRacingEnv(N)          */
+    int32_t num_cars;          /* car env: 1 => CarRacingEnv, 2..MPOPIS_MAX_CARS => MultiCarRacingEnv(N)
+                                  (cs = 2 num_cars H: :cemppi / :μΣaismppi / :pmcmppi need cs <= 800,
+                                  :cmamppi cs <= 710, :nesmppi cs <= 512; MPOPIS_ERR_ARG otherwise) */
     int32_t policy;            /* MPOPIS_POL_*                                                    */
     int32_t num_samples;       /* K                                                               */
     int32_t horizon;           /* H (T in the reference code)                                     */

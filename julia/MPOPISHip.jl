@@ -41,7 +41,7 @@ policy_id(::μΣAISMPPI_Policy) = 6; policy_id(::PMCMPPI_Policy) = 7
 env_kind(::MountainCarEnv) = (0, 0)
 env_kind(::CartPoleEnv) = (2, 0)
 env_kind(::CarRacingEnv) = (1, 1)
-env_kind(env::MultiCarRacingEnv) = (1, env.N)
+env_kind(env::MultiCarRacingEnv) = (1, env.N)      # N passes through: the engine takes 1..MPOPIS_MAX_CARS (8) cars, create refuses more
 
 ais_its(pol) = hasproperty(pol, :opt_its) ? pol.opt_its : 1
 lam_ais(pol) = hasproperty(pol, :λ_ais) ? pol.λ_ais : 0.0

@@ -41,7 +41,7 @@ inline void ensure_dyn_lds(const void* fn, int bytes, std::atomic<unsigned long 
 // starved by them (measured: k_weights 9 us alone, 155 us next to a rollout kernel at equal priority).
 #define MPOPIS_HI_PRIO() __builtin_amdgcn_s_setprio(3)
 
-constexpr int kMaxCars = 4;
+constexpr int kMaxCars = MPOPIS_MAX_CARS;      // include/mpopis.h; the rollout kernels are instantiated for 1..8 cars
 constexpr int kMaxAs = 2 * kMaxCars;
 
 struct EnvDesc {
@@ -111,7 +111,7 @@ __device__ __forceinline__ void status_raise(int* p, int code) {
     }
 }
 
-void launch_rollout(const RolloutArgs& a, hipStream_t s);
+bool launch_rollout(const RolloutArgs& a, hipStream_t s);      // false: no rollout kernel for this env (nothing launched)
 void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t s, const Track& tk);
 // (iters_acc: per-slot running sum of the iteration counts of earlier steps, folded in before iters is cleared; may be null)
 void launch_step_begin(int* status, int* active, const int* alive, int* iters, const double* U, double* Uin, double* Ucur, int B, int cs,
@@ -195,6 +195,7 @@ bool sample_trmm_fusable(int n);
 bool launch_sample_trmm_fused(const double* L, size_t Lstride, double* E, int B, int n, int K, const uint64_t* seeds, uint32_t slo, uint32_t shi,
                               const int* active, hipStream_t s, const double* rng_tab, const double* panel, size_t pstride, const double* oscale2 = nullptr);
 size_t wcov_mfma_workspace_doubles(int B, int cs, int ksplit);
+int wcov_max_cs();                         // largest cs the covariance scatter stages (:cemppi, :μΣaismppi, :pmcmppi)
 void launch_wcov_mfma(const double* X, const double* w, const int32_t* idx, int m, const double* mu, double* S, double* part,
                       int B, int cs, int K, int ksplit, int sel_batch /* batch the kernel choice goes by: the handle's whole batch when this launch covers one part-chain of it (0: B; -1: compact form, see mpopis_handle::wcov_sel_batch) */,
                       double den, double ridge, const int* active, hipStream_t s,

@@ -177,7 +177,8 @@ int mpopis_create(const mpopis_config* cfg, mpopis_handle** out) {
     *out = nullptr;
     const bool car = cfg->env_kind == MPOPIS_ENV_CAR;
     if (!(car || cfg->env_kind == MPOPIS_ENV_MOUNTAINCAR || cfg->env_kind == MPOPIS_ENV_CARTPOLE)) { g_create_error = "unknown env kind"; return MPOPIS_ERR_ARG; }
-    if (car && (cfg->num_cars < 1 || cfg->num_cars > kMaxCars)) { g_create_error = "num_cars must be 1..4"; return MPOPIS_ERR_ARG; }
+    if (car && (cfg->num_cars < 1 || cfg->num_cars > kMaxCars)) { g_create_error = "num_cars must be 1..8"; return MPOPIS_ERR_ARG; }
+    static_assert(kMaxCars == 8, "the message above names the bound");
     if (cfg->policy < MPOPIS_POL_MPPI || cfg->policy > MPOPIS_POL_NESMPPI) { g_create_error = "No policy_type of that kind"; return MPOPIS_ERR_ARG; }
     if (cfg->num_samples < 1 || cfg->horizon < 1 || cfg->batch < 1) { g_create_error = "num_samples, horizon, batch must be >= 1"; return MPOPIS_ERR_ARG; }
     if (cfg->policy == MPOPIS_POL_NESMPPI) {
@@ -187,6 +188,11 @@ int mpopis_create(const mpopis_config* cfg, mpopis_handle** out) {
         if (!std::isfinite(cfg->cma_sigma)) { g_create_error = "nesmppi: step_factor (cma_sigma) must be finite"; return MPOPIS_ERR_ARG; }
     }
     if (cfg->policy == MPOPIS_POL_CMAMPPI && (car ? 2 * cfg->num_cars : 1) * cfg->horizon > invsqrt_max_n()) { g_create_error = "cmamppi: control space too large for the on-chip Σ^-0.5 δw kernel"; return MPOPIS_ERR_ARG; }
+    if ((cfg->policy == MPOPIS_POL_CEMPPI || cfg->policy == MPOPIS_POL_MUSIGMAAISMPPI || cfg->policy == MPOPIS_POL_PMCMPPI) &&
+        (long long)(car ? 2 * cfg->num_cars : 1) * cfg->horizon > wcov_max_cs()) {
+        static const std::string msg = "control space too large for the covariance scatter of :cemppi / :μΣaismppi / :pmcmppi (cs <= " + std::to_string(wcov_max_cs()) + ")";
+        g_create_error = msg; return MPOPIS_ERR_ARG;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available (the engine has no CPU fallback)"; return MPOPIS_ERR_HIP; }
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_error = "bad device ordinal"; return MPOPIS_ERR_ARG; }
@@ -527,6 +533,7 @@ int mpopis_rollout_costs(mpopis_handle* h, const double* x0, const double* U, co
     fill_i32(h->d_status, 0, B, h->stream);
     h->prepare_state();
     h->rollout(h->d_Ucur, h->d_Uin, gv, nullptr);
+    if (!h->launch_err.empty()) { h->err = h->launch_err; h->launch_err.clear(); return MPOPIS_ERR_HIP; }
     HIPCHK(h, hipMemcpyAsync(cost, h->d_cost, sizeof(double) * B * K, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, wait_stream(h->stream));
     HIPCHK(h, hipGetLastError());
@@ -785,7 +792,7 @@ void mpopis_handle::rollout(const double* Ucur, const double* Uorig, const doubl
     a.cmin = weights_in_moments ? d_cmin : nullptr; a.status = weights_in_moments ? d_status : nullptr;
     a.share = coop_share;
     time_begin(0);
-    launch_rollout(a, stream);
+    if (!launch_rollout(a, stream) && launch_err.empty()) launch_err = "rollout: no kernel for this env (num_cars " + std::to_string(env.ncars) + ")";
     time_end();
 }
 

@@ -212,8 +212,12 @@ __device__ __forceinline__ void wcov_rows_chunk(const double* __restrict__ xl, v
     }
 }
 
-template <int KC, bool SQ, bool ROWS = false>
-__global__ void __launch_bounds__(ROWS ? 512 : 256, ROWS ? 1 : 2) k_wcov_mfma_partial(const double* __restrict__ X, const double* __restrict__ w, const int32_t* __restrict__ idx,
+// TALL (cs in 513..kWcovTallRows: six to eight cars at H = 50): the pair-list form with 8 waves per workgroup.  Twice the threads stage twice the
+// rows from the same registers per thread (25 per chunk of 16 columns: 800 rows), and the 8 waves take 56 tile pairs; one workgroup per CU
+// (800 x 17 x 8 B = 106 KB of LDS), i.e. the same two waves per SIMD as the 4-wave form at two workgroups per CU.
+constexpr int kWcovTallRows = 800;
+template <int KC, bool SQ, bool ROWS = false, bool TALL = false>
+__global__ void __launch_bounds__(ROWS || TALL ? 512 : 256, ROWS || TALL ? 1 : 2) k_wcov_mfma_partial(const double* __restrict__ X, const double* __restrict__ w, const int32_t* __restrict__ idx,
                                                            const double* __restrict__ mu, const double* __restrict__ rscale,
                                                            double* __restrict__ part, int cs, int K, int m,
                                                            int ksplit, int npairs, const int* active, int aug,
@@ -225,10 +229,14 @@ __global__ void __launch_bounds__(ROWS ? 512 : 256, ROWS ? 1 : 2) k_wcov_mfma_pa
     const int li = lane & 15, lk = lane >> 4;
     const int nt = (cs + 15) / 16, rows_pad = nt * 16;
     static_assert(!ROWS || (KC == 64 && !SQ), "row form: 64-column chunks, plain scatter");
+    static_assert(!TALL || (KC == 16 && !ROWS), "tall form: 16-column chunks, pair list");
     constexpr int S = ROWS ? kRowsS : KC + 1;                   // LDS row stride (doubles); pair-list form: odd strides measured best (tools/kbench)
-    constexpr int NTHR = ROWS ? 512 : 256;
-    constexpr int kMaxLd = ROWS ? 14 : (KC == 64) ? 28 : 32;    // staged elements per thread and chunk (cs <= 112 resp. 512 rows)
+    constexpr int NTHR = ROWS || TALL ? 512 : 256;
     constexpr int kRowStep = NTHR / KC;
+    // staged elements per thread and chunk (cs <= 112, 512 resp. kWcovTallRows rows)
+    constexpr int kMaxLd = ROWS ? 14 : TALL ? kWcovTallRows / kRowStep : (KC == 64) ? 28 : 32;
+    static_assert(!TALL || kMaxLd * kRowStep == kWcovTallRows, "tall form: whole row steps");
+    constexpr int kPairsThisBlock = (NTHR / 64) * kPairsPerWave; // pair-list forms
     double* Xs = smem;                                          // [rows_pad][S]
     double* ws = smem + (size_t)rows_pad * S;                   // [KC]
     double* wsl = ws + KC;                                      // [per] (weights-from-costs form) the k range's unnormalised weights
@@ -238,7 +246,7 @@ __global__ void __launch_bounds__(ROWS ? 512 : 256, ROWS ? 1 : 2) k_wcov_mfma_pa
     const double* mub = mu + (size_t)b * cs;
     // this wave's tile pairs
     int pa[kPairsPerWave], pb[kPairsPerWave];
-    const int qbase = blockIdx.y * kPairsPerBlock + wv * kPairsPerWave;
+    const int qbase = blockIdx.y * kPairsThisBlock + wv * kPairsPerWave;
 #pragma unroll
     for (int p = 0; p < kPairsPerWave; ++p) {
         if (ROWS) { const int r1 = 3 + (wv & 3), r2 = 2 - (wv & 3); pa[p] = (p <= r1) ? r1 : r2; pb[p] = (p <= r1) ? p : p - r1 - 1; }
@@ -575,6 +583,7 @@ void launch_inv_sd(const double* S, double* rs, int B, int cs, const int* active
 }
 
 static int wcov_kc(int cs) { return cs <= 112 ? 64 : 16; }
+int wcov_max_cs() { return kWcovTallRows; }
 size_t wcov_mfma_workspace_doubles(int B, int cs, int ksplit) {
     const int nt = (cs + 15) / 16;
     return (size_t)B * ksplit * (nt * (nt + 1) / 2) * 256;
@@ -596,6 +605,8 @@ void launch_wcov_mfma(const double* X, const double* w, const int32_t* idx, int 
     // The choice goes by the handle's WHOLE batch (sel_batch), not by this launch's share of it: the part-chains of a multi-stream schedule are in
     // flight together, and a slot's result must not depend on the schedule (the two forms agree to rounding, not bit for bit).
     const bool rows = env_rows && nt == 7 && !rscale && !(ksplit & 1) && sel_batch >= 0 && (long long)(sel_batch > 0 ? sel_batch : B) * (ksplit / 2) >= (env_rows > 1 ? 1 : 192);
+    // cs > 512 (six cars and more at H = 50): the 8-wave pair-list form, up to kWcovTallRows rows (mpopis_create refuses larger cs)
+    const bool tall = nt * 16 > 512;
     const size_t lds = ((size_t)nt * 16 * (rows ? 2 * kRowsS : kc + 1) + kc + (from_cost ? (rows ? 2 * per : per) : 0)) * sizeof(double);
     static std::atomic<unsigned long long> seen[5];
     ensure_dyn_lds((const void*)k_wcov_mfma_partial<64, false, true>, 160 * 1024, seen[4]);
@@ -604,7 +615,17 @@ void launch_wcov_mfma(const double* X, const double* w, const int32_t* idx, int 
     ensure_dyn_lds((const void*)k_wcov_mfma_partial<64, true>, 96 * 1024, seen[2]);
     ensure_dyn_lds((const void*)k_wcov_mfma_partial<16, true>, 96 * 1024, seen[3]);
     const dim3 grid(ksplit, (npairs + kPairsPerBlock - 1) / kPairsPerBlock, B);
-    if (rscale) {
+    if (tall) {
+        static std::atomic<unsigned long long> seen_t[2];
+        const dim3 grid_t(ksplit, (npairs + 8 * kPairsPerWave - 1) / (8 * kPairsPerWave), B);
+        if (rscale) {
+            ensure_dyn_lds((const void*)k_wcov_mfma_partial<16, true, false, true>, 160 * 1024, seen_t[1]);
+            hipLaunchKernelGGL((k_wcov_mfma_partial<16, true, false, true>), grid_t, dim3(512), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
+        } else {
+            ensure_dyn_lds((const void*)k_wcov_mfma_partial<16, false, false, true>, 160 * 1024, seen_t[0]);
+            hipLaunchKernelGGL((k_wcov_mfma_partial<16, false, false, true>), grid_t, dim3(512), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
+        }
+    } else if (rscale) {
         if (kc == 64) hipLaunchKernelGGL((k_wcov_mfma_partial<64, true>), grid, dim3(256), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
         else          hipLaunchKernelGGL((k_wcov_mfma_partial<16, true>), grid, dim3(256), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
     } else {

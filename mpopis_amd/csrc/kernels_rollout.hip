@@ -246,14 +246,14 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4))
 // the sum over its cars in car order, gathered the same way.  SPB waves per workgroup share one LDS copy of the track tables.
 template <int NC, int SPB, bool LOG, int WPE, bool TLDS>
 __global__ void __launch_bounds__(64 * SPB) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_rollout_cars(RolloutArgs a) {
-    static_assert(NC >= 2 && NC <= kMaxCars, "2..4 cars");
+    static_assert(NC >= 2 && NC <= kMaxCars, "2..8 cars");
     constexpr int S = 64 / NC;                                // samples per wave
     const int b = blockIdx.y;
     if (a.active && !a.active[b]) return;
     if (a.iters && blockIdx.x == 0 && threadIdx.x == 0) a.iters[b] = a.iter_n;
     const int lane = threadIdx.x & 63;
     const int g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = min(lane / S, NC - 1), j = lane - c * S;    // car, sample within the wave (NC = 3: lane 63 idles as a duplicate)
+    const int c = min(lane / S, NC - 1), j = lane - c * S;    // car, sample within the wave (64 - NC S lanes idle as duplicates: 1 at NC = 3, 7; 4 at 5, 6)
     const int k = (blockIdx.x * SPB + g) * S + j;
     const int K = a.K, T = a.T;
     const bool valid = j < S && k < K;
@@ -332,7 +332,7 @@ __global__ void __launch_bounds__(64 * SPB) __attribute__((amdgpu_waves_per_eu(W
 // its own lanes, as in k_rollout_cars), accumulates the cost and gathers the sample's total over its cars.  Same arithmetic, same order.
 template <int NC, bool TLDS>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) k_rollout_cars_duo(RolloutArgs a) {
-    static_assert(NC >= 2 && NC <= kMaxCars, "2..4 cars");
+    static_assert(NC >= 2 && NC <= kMaxCars, "2..8 cars");
     constexpr int S = 64 / NC;
     const int b = blockIdx.y;
     if (a.active && !a.active[b]) return;
@@ -548,14 +548,14 @@ static void launch_rollout_kernel(dim3 grid, int block, size_t lds, hipStream_t 
     hipLaunchKernelGGL(KERNEL, grid, dim3(block), lds, st, a);
 }
 
-void launch_rollout(const RolloutArgs& a, hipStream_t st) {
+bool launch_rollout(const RolloutArgs& a, hipStream_t st) {
     if (a.env.kind == MPOPIS_ENV_MOUNTAINCAR) {
         hipLaunchKernelGGL(k_rollout_simple<2>, dim3((a.K + 63) / 64, a.B), dim3(64), 0, st, a);
-        return;
+        return true;
     }
     if (a.env.kind == MPOPIS_ENV_CARTPOLE) {
         hipLaunchKernelGGL(k_rollout_simple<4>, dim3((a.K + 63) / 64, a.B), dim3(64), 0, st, a);
-        return;
+        return true;
     }
     const int P = a.env.track.P, W = a.env.track.nbrw;
     // every table in LDS when that fits the default 64 KB (all bundled tracks: 48-60 points); larger tracks (Track(infile; sample_factor = 1):
@@ -603,12 +603,17 @@ void launch_rollout(const RolloutArgs& a, hipStream_t st) {
         case 2: MPOPIS_LAUNCH_CARS(2); break;
         case 3: MPOPIS_LAUNCH_CARS(3); break;
         case 4: MPOPIS_LAUNCH_CARS(4); break;
-        default: break;
+        case 5: MPOPIS_LAUNCH_CARS(5); break;
+        case 6: MPOPIS_LAUNCH_CARS(6); break;
+        case 7: MPOPIS_LAUNCH_CARS(7); break;
+        case 8: MPOPIS_LAUNCH_CARS(8); break;
+        default: return false;                                  // no kernel for this car count (mpopis_create admits 1..kMaxCars)
     }
 #undef MPOPIS_LAUNCH_CARS
 #undef MPOPIS_LAUNCH_CARS_W
 #undef MPOPIS_LAUNCH_K
 #undef MPOPIS_LAUNCH_CAR
+    return true;
 }
 
 }  // namespace mpopis

@@ -15,6 +15,8 @@ import numpy as np
 from .engine import Engine, default_track, BUNDLED_TRACKS, _f64
 from ._lib import MPOPISError, ERR_ARG
 
+MAX_CARS = 8      # MPOPIS_MAX_CARS (include/mpopis.h)
+
 
 def deg2rad(d):
     return d * (math.pi / 180.0)
@@ -131,8 +133,8 @@ class CarRacingEnv(_EnvBase):
 
 class MultiCarRacingEnv(_EnvBase):
     def __init__(self, N=2, dt=0.1, δt=0.01, track=None, rng=None, device=0):
-        if not 1 <= N <= 4:
-            raise MPOPISError(ERR_ARG, "this engine supports 1..4 cars")
+        if not 1 <= N <= MAX_CARS:
+            raise MPOPISError(ERR_ARG, "this engine supports 1..%d cars" % MAX_CARS)
         self.N = N
         self.params = CarRacingEnvParams()
         self.dt, self.δt = dt, δt
