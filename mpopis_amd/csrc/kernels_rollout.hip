@@ -8,19 +8,19 @@
 // in ONE launch, state in registers, no per-sample env copies (the reference deep-copies the env
 // per sample, :270).
 //
-// Mapping (CDNA4): lane = one car of one sample.  One car (k_rollout_car): a wave = 64 samples; E is [cs][K] (K fastest) so
-// each per-step control load is one coalesced 512-B transaction per wave; the nominal control U, the env state and
-// the 48-point track are wave-uniform and arrive through the scalar cache / LDS broadcasts.  NC cars (k_rollout_cars):
-// a wave = 64/NC samples x NC cars, lane = c * S + j, so the cars of one sample sit in ONE wave and exchange (x,y) for
-// the pairwise terms of the multi-car reward by lane shuffles -- no LDS exchange, no barrier in the time loop (round 2
-// ran wave = car with a workgroup barrier per model step: 5.9 cycles per VALU instruction at 64 trials against 4.8
-// for the one-car kernel).  The kernels are FP64-VALU bound; HBM traffic is 8*cs bytes per sample.
+// Mapping (CDNA4): lane = one car of one sample.  A wave = S = 64/NC samples x NC cars, lane = c * S + j, so the cars of one sample sit in ONE
+// wave and exchange (x,y) for the pairwise terms of the multi-car reward by lane shuffles -- no LDS exchange, no barrier in the time loop (round 2
+// ran wave = car with a workgroup barrier per model step: 5.9 cycles per VALU instruction at 64 trials against 4.8 for the one-car kernel).  One
+// car (S = 64): E is [cs][K] (K fastest) so each per-step control load is one coalesced 512-B transaction per wave; the nominal control U, the env
+// state, the action bounds and the 48-point track are wave-uniform and arrive through the scalar cache / LDS broadcasts.  The kernels are
+// FP64-VALU bound; HBM traffic is 8*cs bytes per sample.
+// Two device bodies serve 1..8 cars: rollout_one_wave (each wave integrates and rewards its samples) and rollout_two_wave (a dynamics wave hands
+// the state to a reward wave, for few rollouts).  The entry points k_rollout_car / k_rollout_car_duo (one car) and k_rollout_cars /
+// k_rollout_cars_duo (2..8 cars) are one call each into them, with their own launch bounds and occupancy.
 #include "engine.h"
 
 namespace mpopis {
 
-// One car (NC = 1, CarRacingEnv): SPB sample-waves per workgroup share one LDS copy of the track tables
-// LOG: the trajectory logger is on (a.traj != nullptr) -- only then is the heading angle psi itself tracked
 // Track tables into LDS (dynamic LDS layout: ring table [(P+6)][4] + certification radii [2][P]; with ALL: + x, y, w, |q|^2 [4][P] + neighbour
 // distances [P][W+1] + neighbour indices [P][W+1]).  Returns the Track the rollout uses; the caller synchronises.
 template <bool ALL>
@@ -67,88 +67,201 @@ extern "C" int mpopis_debug_sick(unsigned char* out, int n, int reset) {       /
     return rc;
 }
 #endif
+
+// ---- the pieces of a rollout, each written once ----
+
+// Slots with active == 0 are skipped (AIS early break); the slot's first thread records the iteration.  False: skip this slot.
+__device__ __forceinline__ bool rollout_slot_begin(const RolloutArgs& a, int b) {
+    if (a.active && !a.active[b]) return false;
+    if (a.iters && blockIdx.x == 0 && threadIdx.x == 0) a.iters[b] = a.iter_n;
+    return true;
+}
+
+// lane = c * S + j: car c of sample j, S = 64 / NC samples per wave (the 64 - NC S lanes past them idle as duplicates: 1 at NC = 3, 7; 4 at 5, 6).
+// wave_id numbers the slot's sample-waves; kk is a sample index that idle lanes may load from.
+template <int NC>
+struct CarLane {
+    static constexpr int S = 64 / NC;
+    int lane, c, j, k, kk;
+    bool valid;
+    __device__ __forceinline__ CarLane(int wave_id, int K)
+        : lane(threadIdx.x & 63), c(min(lane / S, NC - 1)), j(lane - c * S), k(wave_id * S + j), kk(min(k, K - 1)), valid((j < S) & (k < K)) {}
+};
+
+// car c's start state in slot b: the 8 state doubles, sin / cos of psi and delta, and the nearest track point (launch_extend_state)
+template <int NC>
+__device__ __forceinline__ CarState load_start_state(const RolloutArgs& a, int b, int c) {
+    const double* xe = a.x0ext + ((size_t)b * NC + c) * kCarExt;
+    CarState s;
+    s.x = xe[0]; s.y = xe[1]; s.psi = xe[2]; s.Vx = xe[3]; s.Vy = xe[4]; s.r = xe[5]; s.delta = xe[6]; s.pedal = xe[7];
+    s.sp = xe[8]; s.cp = xe[9]; s.sd = xe[10]; s.cd = xe[11]; s.near = (int)xe[12];
+    return s;
+}
+
+// The controls of car c in sample kk (simulate_model, :271-272).  next() forms V = pol.U + E[:,k] of step t from the values the caller holds
+// (e0, e1: noise, u0, u1: nominal control, loaded one step ahead), starts their loads for step t + 1 -- the next step's noise (global) and nominal
+// control (scalar at one car) are in flight during this step -- and adds the control cost of the unclamped V (γ = 0 in every reference config).
+// The prefetched values and T, K stay with the caller: kept as members, they changed the code of the time loops (3.6 % slower two-wave 3-car rollouts).
+template <int NC>
+struct ControlStream {
+    static constexpr int as = 2 * NC;
+    const double *Eb, *Ub, *Uo, *gv;
+    __device__ __forceinline__ ControlStream(const RolloutArgs& a, int b, int c, int kk)
+        : Eb(a.E + (size_t)b * a.cs * a.K + (size_t)(2 * c) * a.K + kk), Ub(a.Ucur + (size_t)b * a.cs + 2 * c), Uo(a.Uorig + (size_t)b * a.cs + 2 * c),
+          gv(a.gvec ? a.gvec + (size_t)b * a.cs + 2 * c : nullptr) {}
+    __device__ __forceinline__ void next(int t, int T, int K, double& e0, double& e1, double& u0, double& u1, double& v0, double& v1, double& cc) const {
+        v0 = u0 + e0; v1 = u1 + e1;
+        if (t + 1 < T) {
+            e0 = Eb[(size_t)(t + 1) * as * K]; e1 = Eb[(size_t)(t + 1) * as * K + K];
+            u0 = Ub[(t + 1) * as]; u1 = Ub[(t + 1) * as + 1];
+        }
+        if (__builtin_expect(gv != nullptr, 0)) cc += control_cost_term(gv[t * as], v0 - Uo[t * as], gv[t * as + 1], v1 - Uo[t * as + 1]);
+    }
+};
+
+// The action bounds of get_model_controls (NaN passes through).  One car: wave-uniform kernel arguments, clamped against scalar registers
+// (clampd_u).  NC cars: the bounds differ between the cars of a wave, so every lane reads its car's from the LDS table bnd (clampd_v), which
+// stage_action_bounds fills before the workgroup barrier.
+template <int NC>
+__device__ __forceinline__ void stage_action_bounds(const EnvDesc& env, double (*bnd)[4]) {
+    if (NC > 1 && threadIdx.x < NC) {
+        const int q = threadIdx.x;
+        bnd[q][0] = env.lo[2 * q]; bnd[q][1] = env.hi[2 * q]; bnd[q][2] = env.lo[2 * q + 1]; bnd[q][3] = env.hi[2 * q + 1];
+    }
+}
+template <int NC>
+__device__ __forceinline__ double clamp_action(const EnvDesc& env, const double (*bnd)[4], int c, int i, double v) {
+    if constexpr (NC == 1) return clampd_u(v, env.lo[i], env.hi[i]);
+    else return clampd_v(v, bnd[c][2 * i], bnd[c][2 * i + 1]);
+}
+
+// multi-car_racing.jl:145-158: the distance from car c to each car behind it in the env's order, and the collision penalty.  The other cars' (x, y)
+// come from the lanes of the same sample by shuffles (every lane takes part in each).  Nothing at one car.
+template <int NC>
+__device__ __forceinline__ double add_pair_terms(double rew, double x, double y, int c, int j) {
+    constexpr int S = 64 / NC;
+#pragma unroll
+    for (int q = 1; q < NC; ++q) {
+        const double xq = __shfl(x, q * S + j, 64), yq = __shfl(y, q * S + j, 64);
+        if (q > c) {
+            const double dx = xq - x, dy = yq - y;
+            const double dd = fast_sqrt(fma(dx, dx, dy * dy));                 // 1 ulp (car_dynamics.h); coincident cars give 1e-150, not 0
+            rew += -dd;
+            if (dd <= 4.0) rew += -11000.0;
+        }
+    }
+    return rew;
+}
+
+// the sample's cost, the sum over its cars in car order: meaningful on the car-0 lanes (cost_0 + cost_1 + ...)
+template <int NC>
+__device__ __forceinline__ double sum_over_cars(double cost, int j) {
+    constexpr int S = 64 / NC;
+    double total = cost;
+#pragma unroll
+    for (int q = 1; q < NC; ++q) total += __shfl(cost, q * S + j, 64);
+    return total;
+}
+
+// The car-0 lane of a valid sample writes its cost.  ρ = minimum(costs) (utils.jl:81) accumulates into cmin, one atomic per wave, so that the AIS
+// reweighting can be folded into the moments kernel (launch_wcov_mfma, weights from costs) instead of a launch of its own between the two.
+template <int NC>
+__device__ __forceinline__ void rollout_epilogue(const RolloutArgs& a, int b, const CarLane<NC>& l, double total) {
+    const bool writer = l.valid && l.c == 0;
+    if (writer) a.cost[(size_t)b * a.K + l.k] = total;
+    if (a.cmin) {
+        unsigned long long key = writer ? cost_key(total) : ~0ull;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key, o, 64); key = (t < key) ? t : key; }
+        if (l.lane == 0) atomicMin(&a.cmin[b], key);
+        if (writer && !(fabs(total) < INFINITY) && a.status) status_raise(&a.status[b], MPOPIS_ERR_ACTION);   // non-finite cost <=> NaN action (car_racing.jl:239)
+    }
+}
+
+// The two-slot LDS mailbox of rollout_two_wave: the dynamics wave publishes (x, y, Vx, Vy) of every lane after model step t, the reward wave
+// consumes them; release / acquire at workgroup scope.  After the last step the dynamics wave leaves its control cost and publishes T + 1.
+struct RolloutMailbox {
+    double state[2][4][64];
+    double cc[64];
+    int ready, done;                                                           // model steps published by wave 0 / consumed by wave 1
+    __device__ __forceinline__ void publish(int t, int lane, const CarState& s) {
+        const int slot = t & 1;
+        if (t >= 2) while (__hip_atomic_load(&done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < t - 1) __builtin_amdgcn_s_sleep(1);   // slot free again?
+        state[slot][0][lane] = s.x; state[slot][1][lane] = s.y; state[slot][2][lane] = s.Vx; state[slot][3][lane] = s.Vy;
+        __hip_atomic_store(&ready, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __device__ __forceinline__ void consume(int t, int lane, double& x, double& y, double& Vx, double& Vy) {
+        while (__hip_atomic_load(&ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < t + 1) __builtin_amdgcn_s_sleep(1);
+        const int slot = t & 1;
+        x = state[slot][0][lane]; y = state[slot][1][lane]; Vx = state[slot][2][lane]; Vy = state[slot][3][lane];
+        __hip_atomic_store(&done, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);       // (release: the reads above are complete)
+    }
+    __device__ __forceinline__ void close(int T, int lane, double c) {
+        cc[lane] = c;
+        __hip_atomic_store(&ready, T + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __device__ __forceinline__ double control_cost(int T, int lane) {
+        while (__hip_atomic_load(&ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < T + 1) __builtin_amdgcn_s_sleep(1);
+        return cc[lane];
+    }
+};
+
+// ---- the two bodies ----
+
+// One wave integrates and rewards S samples x NC cars; SPB sample-waves per workgroup share one LDS copy of the track tables.
+// LOG: the trajectory logger is on (a.traj != nullptr) -- only then is the heading angle psi itself tracked.
 template <int NC, int SPB, bool LOG, bool TLDS>
-__global__ void __launch_bounds__(64 * NC * SPB) __attribute__((amdgpu_waves_per_eu(4, 4))) k_rollout_car(RolloutArgs a) {
-    static_assert(NC == 1, "multi-car envs run k_rollout_cars");
+__device__ __forceinline__ void rollout_one_wave(const RolloutArgs& a) {
 #ifdef MPOPIS_ROLL_PROF
     const unsigned long long prof_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
     const int b = blockIdx.y;
-    if (a.active && !a.active[b]) return;
-    if (a.iters && blockIdx.x == 0 && threadIdx.x == 0) a.iters[b] = a.iter_n;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = 0;                                          // the car
-    const int g = wave;                                       // sample group of this wave
-    const int k = (blockIdx.x * SPB + g) * 64 + lane;
-    const int K = a.K, T = a.T;
-    const bool valid = k < K;
-    const int kk = valid ? k : K - 1;
-    constexpr int as = 2 * NC, ss = 8 * NC;
-    (void)ss;
-
+    if (!rollout_slot_begin(a, b)) return;
+    const int g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);           // sample-wave of the workgroup
+    const CarLane<NC> l(blockIdx.x * SPB + g, a.K);
+    const int T = a.T;
     const CarParams& p = a.env.car;
     // stage the (wave-uniform, read-only) track in LDS: uniform-address ds_reads broadcast to all lanes
     extern __shared__ __attribute__((aligned(16))) double sh_dyn[];
-    const Track tk = stage_track<TLDS>(a.env.track, sh_dyn, threadIdx.x, 64 * NC * SPB);
+    __shared__ double sh_bnd[NC][4];
+    const Track tk = stage_track<TLDS>(a.env.track, sh_dyn, threadIdx.x, 64 * SPB);
+    stage_action_bounds<NC>(a.env, sh_bnd);
     __syncthreads();
-    CarState s;                                               // wave-uniform start state (+ sin/cos), scalar loads
-    {
-        const double* xe = a.x0ext + ((size_t)b * NC + c) * kCarExt;
-        s.x = xe[0]; s.y = xe[1]; s.psi = xe[2]; s.Vx = xe[3]; s.Vy = xe[4]; s.r = xe[5]; s.delta = xe[6]; s.pedal = xe[7];
-        s.sp = xe[8]; s.cp = xe[9]; s.sd = xe[10]; s.cd = xe[11]; s.near = (int)xe[12];
-    }
-    const double* Eb = a.E + (size_t)b * a.cs * K + (size_t)(2 * c) * K + kk;
-    const double* Ub = a.Ucur + (size_t)b * a.cs + 2 * c;
-    const double* Uo = a.Uorig + (size_t)b * a.cs + 2 * c;
-    const double* gv = a.gvec ? a.gvec + (size_t)b * a.cs + 2 * c : nullptr;
-    const double lo0 = a.env.lo[2 * c], hi0 = a.env.hi[2 * c], lo1 = a.env.lo[2 * c + 1], hi1 = a.env.hi[2 * c + 1];
-    double* tr = LOG ? a.traj + ((size_t)b * K + kk) * (size_t)(ss * T) : nullptr;
+    CarState s = load_start_state<NC>(a, b, l.c);
+    double* tr = LOG ? a.traj + ((size_t)b * a.K + l.kk) * (size_t)(8 * NC * T) : nullptr;
+    const ControlStream<NC> ctl(a, b, l.c, l.kk);
 
     double cost = 0.0, cc = 0.0;
-    double e0 = Eb[0], e1 = Eb[K], u0 = Ub[0], u1 = Ub[1];
+    double e0 = ctl.Eb[0], e1 = ctl.Eb[a.K], u0 = ctl.Ub[0], u1 = ctl.Ub[1];
     for (int t = 0; t < T; ++t) {
-        const double v0 = u0 + e0, v1 = u1 + e1;                               // V = pol.U + E[:,k]  :271
-        if (t + 1 < T) {                                                       // next step's noise (global) and nominal control (scalar) in flight during this step
-            e0 = Eb[(size_t)(t + 1) * as * K]; e1 = Eb[(size_t)(t + 1) * as * K + K];
-            u0 = Ub[(t + 1) * as]; u1 = Ub[(t + 1) * as + 1];
-        }
-        if (__builtin_expect(gv != nullptr, 0)) cc += control_cost_term(gv[t * as], v0 - Uo[t * as], gv[t * as + 1], v1 - Uo[t * as + 1]);   // :272 (unclamped V; γ = 0 in every reference config)
-        const double a0 = clampd_u(v0, lo0, hi0), a1 = clampd_u(v1, lo1, hi1); // get_model_controls
+        double v0, v1;
+        ctl.next(t, T, a.K, e0, e1, u0, u1, v0, v1, cc);
+        const double a0 = clamp_action<NC>(a.env, sh_bnd, l.c, 0, v0), a1 = clamp_action<NC>(a.env, sh_bnd, l.c, 1, v1);
         car_action_step<LOG>(p, s, a0, a1, (t & 3) == 0);                      // unit-circle renormalisation every 4th step
-        const double rew = car_reward(p, tk, s.x, s.y, s.Vx, s.Vy, &s.near);
+        const double rew = add_pair_terms<NC>(car_reward(p, tk, s.x, s.y, s.Vx, s.Vy, &s.near), s.x, s.y, l.c, l.j);
         cost -= rew;                                                           // utils.jl:138
-        if (LOG && valid) {                                                    // trajectories[k][t, :] utils.jl:140
+        if (LOG && l.valid) {                                                  // trajectories[k][t, :] utils.jl:140
             double s8[8];
             car_state_to8(s, s8);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) tr[(size_t)(8 * c + i) * T + t] = s8[i];
+            for (int i = 0; i < 8; ++i) tr[(size_t)(8 * l.c + i) * T + t] = s8[i];
         }
     }
     cost += cc;
-    const double total = cost;
+    const double total = sum_over_cars<NC>(cost, l.j);
 #ifdef MPOPIS_PATH_STATS
-    {   // dev build: rollouts of this launch that took the general sub-step at least once / that end stopped (per launch: flags cleared)
+    if constexpr (NC == 1) {   // dev build, one car: rollouts of this launch that took the general sub-step at least once / that end stopped (per launch: flags cleared)
         const size_t t_ = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
         const bool went = t_ < sizeof(g_sick) && (g_sick[t_] & 1);
         if (t_ < sizeof(g_sick)) g_sick[t_] = 0;
         const int nw = __popcll(__ballot(went)), ns = __popcll(__ballot(!(s.Vx > 0.5)));
-        if (lane == 0) { atomicAdd(&g_path_stats[6], (unsigned long long)nw); atomicAdd(&g_path_stats[7], (unsigned long long)ns); }
+        if (l.lane == 0) { atomicAdd(&g_path_stats[6], (unsigned long long)nw); atomicAdd(&g_path_stats[7], (unsigned long long)ns); }
     }
 #endif
-    if (valid) a.cost[(size_t)b * K + k] = total;
-    if (a.cmin) {
-        // ρ = minimum(costs) (utils.jl:81) accumulates here, one atomic per wave, so that the AIS reweighting can be folded into the moments
-        // kernel (launch_wcov_mfma, weights from costs) instead of a launch of its own between the two
-        unsigned long long key = valid ? cost_key(total) : ~0ull;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key, o, 64); key = (t < key) ? t : key; }
-        if (lane == 0) atomicMin(&a.cmin[b], key);
-        if (valid && !(fabs(total) < INFINITY) && a.status) status_raise(&a.status[b], MPOPIS_ERR_ACTION);   // non-finite cost <=> NaN action (car_racing.jl:239)
-    }
+    rollout_epilogue(a, b, l, total);
 #ifdef MPOPIS_ROLL_PROF
-    if (lane == 0) {
-        const int w = (blockIdx.y * gridDim.x + blockIdx.x) * SPB + wave;
+    if (NC == 1 && l.lane == 0) {
+        const int w = (blockIdx.y * gridDim.x + blockIdx.x) * SPB + g;
         if (w < 8192) {
             unsigned hwid; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
             unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
@@ -158,279 +271,90 @@ __global__ void __launch_bounds__(64 * NC * SPB) __attribute__((amdgpu_waves_per
 #endif
 }
 
-// One car, few rollouts (up to two rollout waves per SIMD -- one trial of K <= 4096, or the 8 .. 32-trials-per-GPU share of a strong-scaled
-// run).  A wave alone on a SIMD issues one FP64 instruction per ~8.4 cycles whatever it does, so a rollout costs its instruction count and most
-// of the chip idles.  Here a workgroup is TWO waves for 64 samples: wave 0 integrates the dynamics (V = U + E, clamp, car_action_step) and hands
-// (x, y, Vx, Vy) after every model step to wave 1 through a two-slot LDS mailbox; wave 1 evaluates the reward (nearest-point search, lane test,
-// drift penalty: ~110 of the ~885 instructions of a model step) and accumulates the cost.  Same arithmetic in the same order as k_rollout_car --
-// bit-identical costs -- with the dynamics wave's chain 11 % shorter.  The mailbox is release / acquire at workgroup scope; the reward wave is
-// ~8x faster than the dynamics wave, so the producer practically never waits for a free slot.
-template <bool TLDS>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4))) k_rollout_car_duo(RolloutArgs a) {
-    const int b = blockIdx.y;
-    if (a.active && !a.active[b]) return;
-    if (a.iters && blockIdx.x == 0 && threadIdx.x == 0) a.iters[b] = a.iter_n;
-    const int lane = threadIdx.x & 63;
-    const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);        // 0: dynamics, 1: reward
-    const int k = blockIdx.x * 64 + lane;
-    const int K = a.K, T = a.T;
-    const bool valid = k < K;
-    const int kk = valid ? k : K - 1;
-    constexpr int as = 2;
-    const CarParams& p = a.env.car;
-    extern __shared__ __attribute__((aligned(16))) double sh_dyn[];
-    __shared__ double sh_state[2][4][64];
-    __shared__ double sh_cc[64];
-    __shared__ int sh_ready, sh_done;                                          // model steps published by wave 0 / consumed by wave 1
-    const Track tk = stage_track<TLDS>(a.env.track, sh_dyn, threadIdx.x, 128);
-    if (threadIdx.x == 0) { sh_ready = 0; sh_done = 0; }
-    __syncthreads();
-    if (role == 0) {
-        CarState s;
-        {
-            const double* xe = a.x0ext + (size_t)b * kCarExt;
-            s.x = xe[0]; s.y = xe[1]; s.psi = xe[2]; s.Vx = xe[3]; s.Vy = xe[4]; s.r = xe[5]; s.delta = xe[6]; s.pedal = xe[7];
-            s.sp = xe[8]; s.cp = xe[9]; s.sd = xe[10]; s.cd = xe[11]; s.near = (int)xe[12];
-        }
-        const double* Eb = a.E + (size_t)b * a.cs * K + kk;
-        const double* Ub = a.Ucur + (size_t)b * a.cs;
-        const double* Uo = a.Uorig + (size_t)b * a.cs;
-        const double* gv = a.gvec ? a.gvec + (size_t)b * a.cs : nullptr;
-        const double lo0 = a.env.lo[0], hi0 = a.env.hi[0], lo1 = a.env.lo[1], hi1 = a.env.hi[1];
-        double cc = 0.0;
-        double e0 = Eb[0], e1 = Eb[K], u0 = Ub[0], u1 = Ub[1];
-        for (int t = 0; t < T; ++t) {
-            const double v0 = u0 + e0, v1 = u1 + e1;                           // V = pol.U + E[:,k]  :271
-            if (t + 1 < T) {
-                e0 = Eb[(size_t)(t + 1) * as * K]; e1 = Eb[(size_t)(t + 1) * as * K + K];
-                u0 = Ub[(t + 1) * as]; u1 = Ub[(t + 1) * as + 1];
-            }
-            if (__builtin_expect(gv != nullptr, 0)) cc += control_cost_term(gv[t * as], v0 - Uo[t * as], gv[t * as + 1], v1 - Uo[t * as + 1]);   // :272
-            const double a0 = clampd_u(v0, lo0, hi0), a1 = clampd_u(v1, lo1, hi1);
-            car_action_step<false>(p, s, a0, a1, (t & 3) == 0);
-            const int slot = t & 1;
-            if (t >= 2) while (__hip_atomic_load(&sh_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < t - 1) __builtin_amdgcn_s_sleep(1);   // slot free again?
-            sh_state[slot][0][lane] = s.x; sh_state[slot][1][lane] = s.y; sh_state[slot][2][lane] = s.Vx; sh_state[slot][3][lane] = s.Vy;
-            __hip_atomic_store(&sh_ready, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        sh_cc[lane] = cc;
-        __hip_atomic_store(&sh_ready, T + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return;
-    }
-    double cost = 0.0;
-    int near = (int)a.x0ext[(size_t)b * kCarExt + 12];                         // the anchor of the first search: the track point nearest to the start position
-    for (int t = 0; t < T; ++t) {
-        while (__hip_atomic_load(&sh_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < t + 1) __builtin_amdgcn_s_sleep(1);
-        const int slot = t & 1;
-        const double x = sh_state[slot][0][lane], y = sh_state[slot][1][lane], Vx = sh_state[slot][2][lane], Vy = sh_state[slot][3][lane];
-        __hip_atomic_store(&sh_done, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);       // (release: the reads above are complete)
-        const double rew = car_reward(p, tk, x, y, Vx, Vy, &near);
-        cost -= rew;                                                           // utils.jl:138
-    }
-    while (__hip_atomic_load(&sh_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < T + 1) __builtin_amdgcn_s_sleep(1);
-    cost += sh_cc[lane];
-    const double total = cost;
-    if (valid) a.cost[(size_t)b * K + k] = total;
-    if (a.cmin) {
-        unsigned long long key = valid ? cost_key(total) : ~0ull;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key, o, 64); key = (t < key) ? t : key; }
-        if (lane == 0) atomicMin(&a.cmin[b], key);
-        if (valid && !(fabs(total) < INFINITY) && a.status) status_raise(&a.status[b], MPOPIS_ERR_ACTION);
-    }
-}
-
-// NC >= 2 cars (MultiCarRacingEnv): lane = c * S + j with S = 64 / NC samples per wave, so every car of a sample lives in the same wave.
-// Per-lane (not wave-uniform) here: the start state, the nominal control U (vector loads, one step ahead like E) and the action bounds
-// (LDS table).  The pairwise reward terms (multi-car_racing.jl:145-158) read the other cars' (x, y) by lane shuffles; the sample's cost is
-// the sum over its cars in car order, gathered the same way.  SPB waves per workgroup share one LDS copy of the track tables.
-template <int NC, int SPB, bool LOG, int WPE, bool TLDS>
-__global__ void __launch_bounds__(64 * SPB) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_rollout_cars(RolloutArgs a) {
-    static_assert(NC >= 2 && NC <= kMaxCars, "2..8 cars");
-    constexpr int S = 64 / NC;                                // samples per wave
-    const int b = blockIdx.y;
-    if (a.active && !a.active[b]) return;
-    if (a.iters && blockIdx.x == 0 && threadIdx.x == 0) a.iters[b] = a.iter_n;
-    const int lane = threadIdx.x & 63;
-    const int g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = min(lane / S, NC - 1), j = lane - c * S;    // car, sample within the wave (64 - NC S lanes idle as duplicates: 1 at NC = 3, 7; 4 at 5, 6)
-    const int k = (blockIdx.x * SPB + g) * S + j;
-    const int K = a.K, T = a.T;
-    const bool valid = j < S && k < K;
-    const int kk = min(k, K - 1);
-    constexpr int as = 2 * NC, ss = 8 * NC;
-    (void)ss;
-
-    const CarParams& p = a.env.car;
-    extern __shared__ __attribute__((aligned(16))) double sh_dyn[];
-    __shared__ double sh_bnd[NC][4];                          // lo0, hi0, lo1, hi1 per car
-    const Track tk = stage_track<TLDS>(a.env.track, sh_dyn, threadIdx.x, 64 * SPB);
-    if (threadIdx.x < NC) {
-        const int q = threadIdx.x;
-        sh_bnd[q][0] = a.env.lo[2 * q]; sh_bnd[q][1] = a.env.hi[2 * q]; sh_bnd[q][2] = a.env.lo[2 * q + 1]; sh_bnd[q][3] = a.env.hi[2 * q + 1];
-    }
-    __syncthreads();
-    CarState s;
-    {
-        const double* xe = a.x0ext + ((size_t)b * NC + c) * kCarExt;
-        s.x = xe[0]; s.y = xe[1]; s.psi = xe[2]; s.Vx = xe[3]; s.Vy = xe[4]; s.r = xe[5]; s.delta = xe[6]; s.pedal = xe[7];
-        s.sp = xe[8]; s.cp = xe[9]; s.sd = xe[10]; s.cd = xe[11]; s.near = (int)xe[12];
-    }
-    const double* Eb = a.E + (size_t)b * a.cs * K + (size_t)(2 * c) * K + kk;
-    const double* Ub = a.Ucur + (size_t)b * a.cs + 2 * c;
-    const double* Uo = a.Uorig + (size_t)b * a.cs + 2 * c;
-    const double* gv = a.gvec ? a.gvec + (size_t)b * a.cs + 2 * c : nullptr;
-    double* tr = LOG ? a.traj + ((size_t)b * K + kk) * (size_t)(ss * T) : nullptr;
-
-    double cost = 0.0, cc = 0.0;
-    double e0 = Eb[0], e1 = Eb[K], u0 = Ub[0], u1 = Ub[1];
-    for (int t = 0; t < T; ++t) {
-        const double v0 = u0 + e0, v1 = u1 + e1;                               // V = pol.U + E[:,k]  :271
-        if (t + 1 < T) {                                                       // next step's noise and nominal control in flight during this step
-            e0 = Eb[(size_t)(t + 1) * as * K]; e1 = Eb[(size_t)(t + 1) * as * K + K];
-            u0 = Ub[(t + 1) * as]; u1 = Ub[(t + 1) * as + 1];
-        }
-        if (__builtin_expect(gv != nullptr, 0)) cc += control_cost_term(gv[t * as], v0 - Uo[t * as], gv[t * as + 1], v1 - Uo[t * as + 1]);   // :272
-        const double a0 = clampd_v(v0, sh_bnd[c][0], sh_bnd[c][1]), a1 = clampd_v(v1, sh_bnd[c][2], sh_bnd[c][3]);   // get_model_controls (NaN passes through)
-        car_action_step<LOG>(p, s, a0, a1, (t & 3) == 0);                      // unit-circle renormalisation every 4th step
-        double rew = car_reward(p, tk, s.x, s.y, s.Vx, s.Vy, &s.near);
-#pragma unroll
-        for (int q = 1; q < NC; ++q) {                                         // multi-car_racing.jl:145-158: the cars behind this one in the env's order
-            const double xq = __shfl(s.x, q * S + j, 64), yq = __shfl(s.y, q * S + j, 64);
-            if (q > c) {
-                const double dx = xq - s.x, dy = yq - s.y;
-                const double dd = fast_sqrt(fma(dx, dx, dy * dy));             // 1 ulp (car_dynamics.h); coincident cars give 1e-150, not 0
-                rew += -dd;
-                if (dd <= 4.0) rew += -11000.0;
-            }
-        }
-        cost -= rew;                                                           // utils.jl:138
-        if (LOG && valid) {                                                    // trajectories[k][t, :] utils.jl:140
-            double s8[8];
-            car_state_to8(s, s8);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) tr[(size_t)(8 * c + i) * T + t] = s8[i];
-        }
-    }
-    cost += cc;
-    double total = cost;
-#pragma unroll
-    for (int q = 1; q < NC; ++q) total += __shfl(cost, q * S + j, 64);         // meaningful on the car-0 lanes: cost_0 + cost_1 + ...
-    const bool writer = valid && c == 0;
-    if (writer) a.cost[(size_t)b * K + k] = total;
-    if (a.cmin) {
-        unsigned long long key = writer ? cost_key(total) : ~0ull;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key, o, 64); key = (t < key) ? t : key; }
-        if (lane == 0) atomicMin(&a.cmin[b], key);
-        if (writer && !(fabs(total) < INFINITY) && a.status) status_raise(&a.status[b], MPOPIS_ERR_ACTION);
-    }
-}
-
-// The two-wave form of k_rollout_cars for few rollout waves (k_rollout_car_duo explains why): wave 0 integrates all cars of its S samples, wave 1 takes
-// (x, y, Vx, Vy) of every lane per model step from the LDS mailbox and evaluates the per-car reward AND the pair terms (lane shuffles among
-// its own lanes, as in k_rollout_cars), accumulates the cost and gathers the sample's total over its cars.  Same arithmetic, same order.
+// Few rollouts (up to two rollout waves per SIMD -- one trial of K <= 4096, or the 8 .. 32-trials-per-GPU share of a strong-scaled run).  A wave
+// alone on a SIMD issues one FP64 instruction per ~8.4 cycles whatever it does, so a rollout costs its instruction count and most of the chip
+// idles.  Here a workgroup is TWO waves for S samples: wave 0 integrates the dynamics of every car (V = U + E, clamp, car_action_step) and hands
+// (x, y, Vx, Vy) after every model step to wave 1 through the mailbox; wave 1 evaluates the reward (nearest-point search, lane test, drift
+// penalty: ~110 of the ~885 instructions of a one-car model step) and the pair terms, accumulates the cost and sums it over the cars.  Same
+// arithmetic in the same order as rollout_one_wave -- bit-identical costs -- with the dynamics wave's chain 11 % shorter at one car.  The reward
+// wave is ~8x faster than the dynamics wave, so the producer practically never waits for a free slot.
 template <int NC, bool TLDS>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) k_rollout_cars_duo(RolloutArgs a) {
-    static_assert(NC >= 2 && NC <= kMaxCars, "2..8 cars");
-    constexpr int S = 64 / NC;
+__device__ __forceinline__ void rollout_two_wave(const RolloutArgs& a) {
     const int b = blockIdx.y;
-    if (a.active && !a.active[b]) return;
-    if (a.iters && blockIdx.x == 0 && threadIdx.x == 0) a.iters[b] = a.iter_n;
-    const int lane = threadIdx.x & 63;
+    if (!rollout_slot_begin(a, b)) return;
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);        // 0: dynamics, 1: reward
-    const int c = min(lane / S, NC - 1), j = lane - c * S;
-    const int k = blockIdx.x * S + j;
-    const int K = a.K, T = a.T;
-    const bool valid = j < S && k < K;
-    const int kk = min(k, K - 1);
-    constexpr int as = 2 * NC;
+    const CarLane<NC> l(blockIdx.x, a.K);
+    const int T = a.T;
     const CarParams& p = a.env.car;
     extern __shared__ __attribute__((aligned(16))) double sh_dyn[];
     __shared__ double sh_bnd[NC][4];
-    __shared__ double sh_state[2][4][64];
-    __shared__ double sh_cc[64];
-    __shared__ int sh_ready, sh_done;
+    __shared__ RolloutMailbox mb;
     const Track tk = stage_track<TLDS>(a.env.track, sh_dyn, threadIdx.x, 128);
-    if (threadIdx.x < NC) {
-        const int q = threadIdx.x;
-        sh_bnd[q][0] = a.env.lo[2 * q]; sh_bnd[q][1] = a.env.hi[2 * q]; sh_bnd[q][2] = a.env.lo[2 * q + 1]; sh_bnd[q][3] = a.env.hi[2 * q + 1];
-    }
-    if (threadIdx.x == 0) { sh_ready = 0; sh_done = 0; }
+    stage_action_bounds<NC>(a.env, sh_bnd);
+    if (threadIdx.x == 0) { mb.ready = 0; mb.done = 0; }
     __syncthreads();
     if (role == 0) {
-        CarState s;
-        {
-            const double* xe = a.x0ext + ((size_t)b * NC + c) * kCarExt;
-            s.x = xe[0]; s.y = xe[1]; s.psi = xe[2]; s.Vx = xe[3]; s.Vy = xe[4]; s.r = xe[5]; s.delta = xe[6]; s.pedal = xe[7];
-            s.sp = xe[8]; s.cp = xe[9]; s.sd = xe[10]; s.cd = xe[11]; s.near = (int)xe[12];
-        }
-        const double* Eb = a.E + (size_t)b * a.cs * K + (size_t)(2 * c) * K + kk;
-        const double* Ub = a.Ucur + (size_t)b * a.cs + 2 * c;
-        const double* Uo = a.Uorig + (size_t)b * a.cs + 2 * c;
-        const double* gv = a.gvec ? a.gvec + (size_t)b * a.cs + 2 * c : nullptr;
+        CarState s = load_start_state<NC>(a, b, l.c);
+        const ControlStream<NC> ctl(a, b, l.c, l.kk);
         double cc = 0.0;
-        double e0 = Eb[0], e1 = Eb[K], u0 = Ub[0], u1 = Ub[1];
+        double e0 = ctl.Eb[0], e1 = ctl.Eb[a.K], u0 = ctl.Ub[0], u1 = ctl.Ub[1];
         for (int t = 0; t < T; ++t) {
-            const double v0 = u0 + e0, v1 = u1 + e1;                           // V = pol.U + E[:,k]  :271
-            if (t + 1 < T) {
-                e0 = Eb[(size_t)(t + 1) * as * K]; e1 = Eb[(size_t)(t + 1) * as * K + K];
-                u0 = Ub[(t + 1) * as]; u1 = Ub[(t + 1) * as + 1];
-            }
-            if (__builtin_expect(gv != nullptr, 0)) cc += control_cost_term(gv[t * as], v0 - Uo[t * as], gv[t * as + 1], v1 - Uo[t * as + 1]);   // :272
-            const double a0 = clampd_v(v0, sh_bnd[c][0], sh_bnd[c][1]), a1 = clampd_v(v1, sh_bnd[c][2], sh_bnd[c][3]);
+            double v0, v1;
+            ctl.next(t, T, a.K, e0, e1, u0, u1, v0, v1, cc);
+            const double a0 = clamp_action<NC>(a.env, sh_bnd, l.c, 0, v0), a1 = clamp_action<NC>(a.env, sh_bnd, l.c, 1, v1);
             car_action_step<false>(p, s, a0, a1, (t & 3) == 0);
-            const int slot = t & 1;
-            if (t >= 2) while (__hip_atomic_load(&sh_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < t - 1) __builtin_amdgcn_s_sleep(1);
-            sh_state[slot][0][lane] = s.x; sh_state[slot][1][lane] = s.y; sh_state[slot][2][lane] = s.Vx; sh_state[slot][3][lane] = s.Vy;
-            __hip_atomic_store(&sh_ready, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            mb.publish(t, l.lane, s);
         }
-        sh_cc[lane] = cc;
-        __hip_atomic_store(&sh_ready, T + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        mb.close(T, l.lane, cc);
         return;
     }
     double cost = 0.0;
-    int near = (int)a.x0ext[((size_t)b * NC + c) * kCarExt + 12];
+    int near = load_start_state<NC>(a, b, l.c).near;                            // the anchor of the first search: the track point nearest to the start position
     for (int t = 0; t < T; ++t) {
-        while (__hip_atomic_load(&sh_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < t + 1) __builtin_amdgcn_s_sleep(1);
-        const int slot = t & 1;
-        const double x = sh_state[slot][0][lane], y = sh_state[slot][1][lane], Vx = sh_state[slot][2][lane], Vy = sh_state[slot][3][lane];
-        __hip_atomic_store(&sh_done, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        double rew = car_reward(p, tk, x, y, Vx, Vy, &near);
-#pragma unroll
-        for (int q = 1; q < NC; ++q) {                                         // multi-car_racing.jl:145-158
-            const double xq = __shfl(x, q * S + j, 64), yq = __shfl(y, q * S + j, 64);
-            if (q > c) {
-                const double dx = xq - x, dy = yq - y;
-                const double dd = fast_sqrt(fma(dx, dx, dy * dy));
-                rew += -dd;
-                if (dd <= 4.0) rew += -11000.0;
-            }
-        }
+        double x, y, Vx, Vy;
+        mb.consume(t, l.lane, x, y, Vx, Vy);
+        const double rew = add_pair_terms<NC>(car_reward(p, tk, x, y, Vx, Vy, &near), x, y, l.c, l.j);
         cost -= rew;                                                           // utils.jl:138
     }
-    while (__hip_atomic_load(&sh_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < T + 1) __builtin_amdgcn_s_sleep(1);
-    cost += sh_cc[lane];
-    double total = cost;
-#pragma unroll
-    for (int q = 1; q < NC; ++q) total += __shfl(cost, q * S + j, 64);
-    const bool writer = valid && c == 0;
-    if (writer) a.cost[(size_t)b * K + k] = total;
-    if (a.cmin) {
-        unsigned long long key = writer ? cost_key(total) : ~0ull;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key, o, 64); key = (t < key) ? t : key; }
-        if (lane == 0) atomicMin(&a.cmin[b], key);
-        if (writer && !(fabs(total) < INFINITY) && a.status) status_raise(&a.status[b], MPOPIS_ERR_ACTION);
-    }
+    cost += mb.control_cost(T, l.lane);
+    rollout_epilogue(a, b, l, sum_over_cars<NC>(cost, l.j));
+}
+
+// ---- the entry points ----
+
+// One car (CarRacingEnv), 4 waves per SIMD
+template <int NC, int SPB, bool LOG, bool TLDS>
+__global__ void __launch_bounds__(64 * NC * SPB) __attribute__((amdgpu_waves_per_eu(4, 4))) k_rollout_car(RolloutArgs a) {
+    static_assert(NC == 1, "multi-car envs run k_rollout_cars");
+    rollout_one_wave<NC, SPB, LOG, TLDS>(a);
+}
+
+// One car, two waves: held to 128 VGPRs = 4 waves per SIMD, so two dynamics and two reward waves share a SIMD
+template <bool TLDS>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4))) k_rollout_car_duo(RolloutArgs a) {
+    rollout_two_wave<1, TLDS>(a);
+}
+
+// NC >= 2 cars (MultiCarRacingEnv).  The launch runs it at WPE = 3 waves per SIMD: 168 VGPRs, no spills, 1411 us at 64 three-car trials,
+// against 1509 us at 4 (128 VGPRs, 33 spills).
+template <int NC, int SPB, bool LOG, int WPE, bool TLDS>
+__global__ void __launch_bounds__(64 * SPB) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_rollout_cars(RolloutArgs a) {
+    static_assert(NC >= 2 && NC <= kMaxCars, "2..8 cars");
+    rollout_one_wave<NC, SPB, LOG, TLDS>(a);
+}
+
+// NC >= 2 cars, two waves, 3 waves per SIMD
+template <int NC, bool TLDS>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) k_rollout_cars_duo(RolloutArgs a) {
+    static_assert(NC >= 2 && NC <= kMaxCars, "2..8 cars");
+    rollout_two_wave<NC, TLDS>(a);
 }
 
 // MountainCar (ss = 2) and CartPole (ss = 4): scalar action, a handful of flops per step
 template <int SS>
 __global__ void __launch_bounds__(64) k_rollout_simple(RolloutArgs a) {
     const int b = blockIdx.y;
-    if (a.active && !a.active[b]) return;
-    if (a.iters && blockIdx.x == 0 && threadIdx.x == 0) a.iters[b] = a.iter_n;
+    if (!rollout_slot_begin(a, b)) return;
     const int k = blockIdx.x * 64 + threadIdx.x;
     const int K = a.K, T = a.T;
     const bool valid = k < K;
@@ -548,72 +472,63 @@ static void launch_rollout_kernel(dim3 grid, int block, size_t lds, hipStream_t 
     hipLaunchKernelGGL(KERNEL, grid, dim3(block), lds, st, a);
 }
 
-bool launch_rollout(const RolloutArgs& a, hipStream_t st) {
-    if (a.env.kind == MPOPIS_ENV_MOUNTAINCAR) {
-        hipLaunchKernelGGL(k_rollout_simple<2>, dim3((a.K + 63) / 64, a.B), dim3(64), 0, st, a);
-        return true;
+// The one-wave form: one wave per S = 64 / NC samples, SPB waves per workgroup.  LOG: the trajectory logger; TLDS: every track table in LDS.
+template <int NC, int SPB, bool LOG, bool TLDS>
+static void launch_one_wave_kernel(const RolloutArgs& a, size_t lds, hipStream_t st) {
+    const dim3 grid((a.K + SPB * (64 / NC) - 1) / (SPB * (64 / NC)), a.B);
+    if constexpr (NC == 1) launch_rollout_kernel<k_rollout_car<1, SPB, LOG, TLDS>>(grid, 64 * SPB, lds, st, a);
+    else launch_rollout_kernel<k_rollout_cars<NC, SPB, LOG, 3, TLDS>>(grid, 64 * SPB, lds, st, a);
+}
+template <int NC, int SPB>
+static void launch_one_wave(const RolloutArgs& a, bool tl, size_t lds, hipStream_t st) {
+    if (a.traj) { if (tl) launch_one_wave_kernel<NC, SPB, true, true>(a, lds, st); else launch_one_wave_kernel<NC, SPB, true, false>(a, lds, st); }
+    else        { if (tl) launch_one_wave_kernel<NC, SPB, false, true>(a, lds, st); else launch_one_wave_kernel<NC, SPB, false, false>(a, lds, st); }
+}
+// The two-wave form: two waves per S samples (no logger).
+template <int NC>
+static void launch_two_wave(const RolloutArgs& a, bool tl, size_t lds, hipStream_t st) {
+    const dim3 grid((a.K + 64 / NC - 1) / (64 / NC), a.B);
+    if constexpr (NC == 1) { if (tl) launch_rollout_kernel<k_rollout_car_duo<true>>(grid, 128, lds, st, a); else launch_rollout_kernel<k_rollout_car_duo<false>>(grid, 128, lds, st, a); }
+    else { if (tl) launch_rollout_kernel<k_rollout_cars_duo<NC, true>>(grid, 128, lds, st, a); else launch_rollout_kernel<k_rollout_cars_duo<NC, false>>(grid, 128, lds, st, a); }
+}
+
+// The two-wave form takes launches of up to this many rollout waves per CU (all parts of a multi-stream schedule together).  Measured crossovers:
+// one car 8, i.e. 2 per SIMD (C5 shapes: 3.49 vs 3.95 ms at 32 trials, 5.36 vs 4.71 at 48); 2..8 cars (3 waves per SIMD) 5 (C4 shapes: 5.53 ->
+// 4.86 ms at one trial, 7.18 -> 6.66 at 6 (1176 waves), 7.49 -> 7.68 at 8).  MPOPIS_ROLLOUT_DUO, read once per process, replaces the limit by a
+// wave count for the whole chip; 0: never.
+constexpr int kDuoCarWaves = 8, kDuoCarsWaves = 5;
+static long long rollout_duo_max_waves(int ncars) {
+    static const int env_duo = [] { const char* e = getenv("MPOPIS_ROLLOUT_DUO"); return e ? atoi(e) : -1; }();
+    return env_duo >= 0 ? env_duo : (long long)(ncars == 1 ? kDuoCarWaves : kDuoCarsWaves) * coop_max_workgroups();
+}
+
+// NC cars (compile-time dispatch over 1..kMaxCars): the two-wave form for few rollout waves, otherwise the one-wave form with one sample-wave per
+// workgroup for small K (every wave on its own CU) or 4 sharing the LDS tables for large K.  False: no kernel for this car count.
+template <int NC = 1>
+static bool launch_car_rollout(const RolloutArgs& a, bool tl, size_t lds, hipStream_t st) {
+    if (a.env.ncars != NC) {
+        if constexpr (NC < kMaxCars) return launch_car_rollout<NC + 1>(a, tl, lds, st);
+        else return false;
     }
-    if (a.env.kind == MPOPIS_ENV_CARTPOLE) {
-        hipLaunchKernelGGL(k_rollout_simple<4>, dim3((a.K + 63) / 64, a.B), dim3(64), 0, st, a);
+    constexpr int S = 64 / NC;
+    const long long waves = (long long)a.B * ((a.K + S - 1) / S) * std::max(1, a.share);
+    if (!a.traj && waves <= rollout_duo_max_waves(NC)) launch_two_wave<NC>(a, tl, lds, st);
+    else if (a.K >= 1024) launch_one_wave<NC, 4>(a, tl, lds, st);
+    else launch_one_wave<NC, 1>(a, tl, lds, st);
+    return true;
+}
+
+bool launch_rollout(const RolloutArgs& a, hipStream_t st) {
+    if (a.env.kind == MPOPIS_ENV_MOUNTAINCAR || a.env.kind == MPOPIS_ENV_CARTPOLE) {
+        const auto kernel = a.env.kind == MPOPIS_ENV_CARTPOLE ? k_rollout_simple<4> : k_rollout_simple<2>;     // state size 4 / 2
+        hipLaunchKernelGGL(kernel, dim3((a.K + 63) / 64, a.B), dim3(64), 0, st, a);
         return true;
     }
     const int P = a.env.track.P, W = a.env.track.nbrw;
     // every table in LDS when that fits the default 64 KB (all bundled tracks: 48-60 points); larger tracks (Track(infile; sample_factor = 1):
     // ~1000 points) stage the ring table only (48 P + 192 B: 96.2 KB at the 2048-point limit; the kernels' dynamic-LDS limit is raised to 112 KB once)
     const bool tl = track_lds_bytes(P, W, true) <= kRolloutDynLdsDefault;      // (static LDS of the two-wave kernels counted: P = 221, 222 used to total 65.7-66 KB without the limit being raised)
-    const size_t lds = track_lds_bytes(P, W, tl);
-    // small K: one sample-wave per workgroup keeps every wave on its own CU; large K: 4 waves share the LDS tables
-    const bool wide = a.K >= 1024;
-    const dim3 g1((a.K + 63) / 64, a.B), g4((a.K + 255) / 256, a.B);
-#define MPOPIS_LAUNCH_K(KERNEL, GRID, BLOCK) launch_rollout_kernel<KERNEL>(GRID, BLOCK, lds, st, a)
-#define MPOPIS_LAUNCH_CAR(NC, SPB, GRID, BLOCK)                                                        \
-    do {                                                                                               \
-        if (a.traj) { if (tl) MPOPIS_LAUNCH_K((k_rollout_car<NC, SPB, true, true>), GRID, BLOCK); else MPOPIS_LAUNCH_K((k_rollout_car<NC, SPB, true, false>), GRID, BLOCK); }   \
-        else        { if (tl) MPOPIS_LAUNCH_K((k_rollout_car<NC, SPB, false, true>), GRID, BLOCK); else MPOPIS_LAUNCH_K((k_rollout_car<NC, SPB, false, false>), GRID, BLOCK); } \
-    } while (0)
-#define MPOPIS_LAUNCH_CARS_W(NC, WPE, SPB, GRID, BLOCK)                                                                                                      \
-    do {                                                                                                                                                    \
-        if (a.traj) { if (tl) MPOPIS_LAUNCH_K((k_rollout_cars<NC, SPB, true, WPE, true>), GRID, BLOCK); else MPOPIS_LAUNCH_K((k_rollout_cars<NC, SPB, true, WPE, false>), GRID, BLOCK); }   \
-        else        { if (tl) MPOPIS_LAUNCH_K((k_rollout_cars<NC, SPB, false, WPE, true>), GRID, BLOCK); else MPOPIS_LAUNCH_K((k_rollout_cars<NC, SPB, false, WPE, false>), GRID, BLOCK); } \
-    } while (0)
-    // waves per SIMD of the multi-car kernel: 3 (168 VGPRs, no spills; 1411 us at 64 three-car trials) beats 4 (128 VGPRs, 33 spills: 1509 us)
-#define MPOPIS_LAUNCH_CARS(NC)                                                                                   \
-    do {                                                                                                         \
-        const int S_ = 64 / NC;                                                                                  \
-        const dim3 gw((a.K + 4 * S_ - 1) / (4 * S_), a.B), gn((a.K + S_ - 1) / S_, a.B);                          \
-        const long long waves_ = (long long)a.B * ((a.K + S_ - 1) / S_) * std::max(1, a.share);                  \
-        if (!a.traj && waves_ <= (env_duo >= 0 ? env_duo : kDuoCarsWaves * coop_max_workgroups())) {             \
-            if (tl) MPOPIS_LAUNCH_K((k_rollout_cars_duo<NC, true>), gn, 128); else MPOPIS_LAUNCH_K((k_rollout_cars_duo<NC, false>), gn, 128); \
-        } else if (wide) MPOPIS_LAUNCH_CARS_W(NC, 3, 4, gw, 256); else MPOPIS_LAUNCH_CARS_W(NC, 3, 1, gn, 64);    \
-    } while (0)
-    // two-wave kernels: MPOPIS_ROLLOUT_DUO = largest rollout-wave count (all parts of a multi-stream schedule together) that still takes them; 0: never
-    static const int env_duo = [] { const char* e = getenv("MPOPIS_ROLLOUT_DUO"); return e ? atoi(e) : -1; }();
-    constexpr int kDuoCarsWaves = 5;                           // multi-car (3 waves per SIMD): measured, C4 shapes -- 5.53 -> 4.86 ms at one trial, 7.18 -> 6.66 at 6 (1176 waves), 7.49 -> 7.68 at 8
-    switch (a.env.ncars) {
-        case 1: {
-            // up to 2 rollout waves per SIMD (measured crossover, C5 shapes: 3.49 vs 3.95 ms at 32 trials, 5.36 vs 4.71 at 48; the duo kernel is held to
-            // 128 VGPRs = 4 waves per SIMD, so two dynamics and two reward waves share a SIMD there):
-            // dynamics and reward in two waves per 64 samples (k_rollout_car_duo); MPOPIS_ROLLOUT_DUO=0: never
-            const long long waves = (long long)a.B * ((a.K + 63) / 64) * std::max(1, a.share);
-            if (!a.traj && waves <= (env_duo >= 0 ? env_duo : 8 * coop_max_workgroups())) {
-                if (tl) MPOPIS_LAUNCH_K((k_rollout_car_duo<true>), g1, 128); else MPOPIS_LAUNCH_K((k_rollout_car_duo<false>), g1, 128);
-            } else if (wide) MPOPIS_LAUNCH_CAR(1, 4, g4, 256); else MPOPIS_LAUNCH_CAR(1, 1, g1, 64);
-            break;
-        }
-        case 2: MPOPIS_LAUNCH_CARS(2); break;
-        case 3: MPOPIS_LAUNCH_CARS(3); break;
-        case 4: MPOPIS_LAUNCH_CARS(4); break;
-        case 5: MPOPIS_LAUNCH_CARS(5); break;
-        case 6: MPOPIS_LAUNCH_CARS(6); break;
-        case 7: MPOPIS_LAUNCH_CARS(7); break;
-        case 8: MPOPIS_LAUNCH_CARS(8); break;
-        default: return false;                                  // no kernel for this car count (mpopis_create admits 1..kMaxCars)
-    }
-#undef MPOPIS_LAUNCH_CARS
-#undef MPOPIS_LAUNCH_CARS_W
-#undef MPOPIS_LAUNCH_K
-#undef MPOPIS_LAUNCH_CAR
-    return true;
+    return launch_car_rollout(a, tl, track_lds_bytes(P, W, tl), st);
 }
 
 }  // namespace mpopis
