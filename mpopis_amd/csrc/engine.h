@@ -120,6 +120,10 @@ void launch_step_begin(int* status, int* active, const int* alive, int* iters, c
 // compute_weights (utils.jl:79-86) per slot: w = exp(-(1/λ)(c-min c)) / Σ
 void launch_weights(const double* cost, double* w, int B, int K, double lambda, const int* active,
                     int* status, hipStream_t s, double* wsum = nullptr);
+// which form of k_weights launch_weights runs for K samples (the workgroup size decides: the register form covers K <= 8 x blockDim)
+enum WeightsForm { WEIGHTS_REG_256 = 0, WEIGHTS_REG_1024 = 1, WEIGHTS_3PASS_1024 = 2 };
+int weights_block(int K);
+WeightsForm weights_form(int K);
 
 // out[b][r] = Σ_k w[b][k] * (E[b][r][k] + shift[b][r]) / (norm ? Σ_k w : 1)
 void launch_wmean(const double* E, const double* w, const double* shiftA, const double* shiftB,
@@ -227,6 +231,15 @@ void launch_sortperm(const double* cost, int32_t* order, int B, int K, int m_eli
 void launch_alias_build(const double* w, double* accept, int32_t* alias, int B, int K, const int* active, hipStream_t s, int* need_ws = nullptr,
                         int32_t* stack_ws = nullptr /* B x 2K ints, needed when K > alias_lds_max_K() */);
 int alias_lds_max_K();
+// The kernel each launcher picks, as pure functions of the launch's shape (the launchers call them; tools/kbench_select.hip prints them so that a
+// test written for one form fails when a threshold moves instead of silently testing another form).
+//   have_ws: skey and done both given.  multi_enabled / par_enabled: MPOPIS_SORT_MULTI / MPOPIS_ALIAS_PAR (default 1), read once per process.
+enum SortForm { SORT_RANK = 0, SORT_LDS = 1, SORT_BITONIC4 = 2, SORT_BITONIC8 = 3, SORT_RANK_MULTI = 4, SORT_RANK_BIG = 5 };
+enum AliasForm { ALIAS_SEQ_LDS = 0, ALIAS_SEQ_GLOBAL = 1, ALIAS_PAR_THEN_SEQ_LDS = 2 };
+bool sortperm_multi_enabled();
+bool alias_par_enabled();
+SortForm sortperm_form(int B, int K, bool have_ws, bool multi_enabled);
+AliasForm alias_build_form(int K, bool have_need_ws, bool par_enabled);
 void launch_alias_sample(const double* accept, const int32_t* alias, const int32_t* di, size_t di_stride, const double* du,
                          int32_t* out, int32_t* log, size_t log_stride, int B, int K, const int* active, hipStream_t s);
 

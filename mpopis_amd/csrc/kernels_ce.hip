@@ -61,13 +61,14 @@ __global__ void __launch_bounds__(kCeThreads) k_ce_cov_small(const double* __res
         __syncthreads();
         if (m >= 2 && active) {                                  // elite early break on the sorted costs (as elite_break_tail, kernels_select.hip)
             double mx = -INFINITY;
-            for (int j = threadIdx.x; j + 1 < m; j += kCeThreads) mx = fmax(mx, fabs(sc[j + 1] - sc[j]));
+            auto nan_max = [](double a, double d) { return (d > a || d != d) ? d : a; };      // keeps a NaN (fmax drops it): see elite_break_tail
+            for (int j = threadIdx.x; j + 1 < m; j += kCeThreads) mx = nan_max(mx, fabs(sc[j + 1] - sc[j]));
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+            for (int o = 32; o > 0; o >>= 1) mx = nan_max(mx, __shfl_xor(mx, o, 64));
             if ((threadIdx.x & 63) == 0) eb_red[threadIdx.x >> 6] = mx;
             __syncthreads();
             if (threadIdx.x == 0) {
-                for (int w = 1; w < kCeThreads / 64; ++w) mx = fmax(mx, eb_red[w]);
+                for (int w = 1; w < kCeThreads / 64; ++w) mx = nan_max(mx, eb_red[w]);
                 if (mx < 10e-3) { active[b] = 0; sh_broke = 1; }
             }
             __syncthreads();

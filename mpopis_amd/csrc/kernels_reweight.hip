@@ -83,8 +83,13 @@ __global__ void __launch_bounds__(1024) k_weights(const double* __restrict__ cos
     if (bad && status) status_raise(&status[b], MPOPIS_ERR_ACTION);               // non-finite cost <=> NaN action (car_racing.jl:239)
 }
 
+int weights_block(int K) { return K >= 1024 ? 1024 : 256; }
+WeightsForm weights_form(int K) {                                                // k_weights: the register form while K <= 8 x blockDim
+    if (K <= 8 * weights_block(K)) return weights_block(K) == 1024 ? WEIGHTS_REG_1024 : WEIGHTS_REG_256;
+    return WEIGHTS_3PASS_1024;                                                   // (K > 8192: the block is 1024 there)
+}
 void launch_weights(const double* cost, double* w, int B, int K, double lambda, const int* active, int* status, hipStream_t s, double* wsum) {
-    hipLaunchKernelGGL(k_weights, dim3(B), dim3(K >= 1024 ? 1024 : 256), 0, s, cost, w, K, -1 / lambda, active, status, wsum);
+    hipLaunchKernelGGL(k_weights, dim3(B), dim3(weights_block(K)), 0, s, cost, w, K, -1 / lambda, active, status, wsum);
 }
 
 __global__ void __launch_bounds__(256) k_wmean(const double* __restrict__ E, const double* __restrict__ w,

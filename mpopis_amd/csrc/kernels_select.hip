@@ -11,18 +11,22 @@ namespace mpopis {
 // CE/CMA early break (:458-461 / :566-569), fused into the sort kernels: if max_j |c[order[j+1]] - c[order[j]]| < 10e-3 over the elite
 // set, the slot leaves the AIS loop (active[b] = 0) -- nothing of this iteration's update is applied.  skey: the sorted costs in LDS
 // (visible to the whole workgroup); m_elite <= 0: no check.
+// max that keeps a NaN from either side (fmax drops it): Julia's maximum propagates NaN and `NaN < 10e-3` is false, so an elite set whose sorted costs
+// hold +inf next to +inf (inf - inf) or a NaN never breaks -- the argument of kernels_nes.hip for its own cost statistics.
+__device__ __forceinline__ double nan_max(double mx, double d) { return (d > mx || d != d) ? d : mx; }
+
 __device__ __forceinline__ void elite_break_tail(const double* skey, int m_elite, int* active, int b) {
     __shared__ double eb_red[16];
     if (m_elite < 2 || !active) return;
     double mx = -INFINITY;
-    for (int j = threadIdx.x; j + 1 < m_elite; j += blockDim.x) mx = fmax(mx, fabs(skey[j + 1] - skey[j]));
+    for (int j = threadIdx.x; j + 1 < m_elite; j += blockDim.x) mx = nan_max(mx, fabs(skey[j + 1] - skey[j]));
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+    for (int o = 32; o > 0; o >>= 1) mx = nan_max(mx, __shfl_xor(mx, o, 64));
     if ((threadIdx.x & 63) == 0) eb_red[threadIdx.x >> 6] = mx;
     __syncthreads();
     if (threadIdx.x == 0) {
         const int nw = (blockDim.x + 63) >> 6;
-        for (int w = 1; w < nw; ++w) mx = fmax(mx, eb_red[w]);
+        for (int w = 1; w < nw; ++w) mx = nan_max(mx, eb_red[w]);
         if (mx < 10e-3) active[b] = 0;
     }
 }
@@ -45,7 +49,11 @@ __global__ void __launch_bounds__(1024) k_sortperm(const double* __restrict__ co
     double k[EPT];
     int id[EPT];
 #pragma unroll
-    for (int r = 0; r < EPT; ++r) { const int e = base + r; k[r] = (e < K) ? cost[(size_t)b * K + e] : INFINITY; id[r] = e; }
+    for (int r = 0; r < EPT; ++r) {                                             // NaN ranks like +inf (see k_sortperm_rank): a compare-exchange whose two partners
+        const int e = base + r;                                                 // both see "not greater" would keep the same element twice
+        const double v = (e < K) ? cost[(size_t)b * K + e] : INFINITY;
+        k[r] = (v != v) ? INFINITY : v; id[r] = e;
+    }
     // a <- min(a, b) if keep_min else max(a, b), under (key, index) order (indices are distinct: never equal)
     auto cmpx = [](double& ka, int& ia, double kb, int ib, bool keep_min) {
         const bool a_gt_b = (ka > kb) || (ka == kb && ia > ib);
@@ -106,7 +114,7 @@ __global__ void __launch_bounds__(1024) k_sortperm_lds(const double* __restrict_
     int32_t* idx = reinterpret_cast<int32_t*>(smem + (size_t)n * sizeof(double));
     const int b = blockIdx.x;
     if (active && !active[b]) return;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) { key[i] = (i < K) ? cost[(size_t)b * K + i] : INFINITY; idx[i] = i; }
+    for (int i = threadIdx.x; i < n; i += blockDim.x) { const double v = (i < K) ? cost[(size_t)b * K + i] : INFINITY; key[i] = (v != v) ? INFINITY : v; idx[i] = i; }   // NaN ranks like +inf (see k_sortperm_rank)
     __syncthreads();
     for (int size = 2; size <= n; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
@@ -179,14 +187,14 @@ __device__ __forceinline__ void elite_break_last_workgroup(double* __restrict__ 
     for (int q = tid; q + 1 < m_elite; q += 256) {
         const double a0 = __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)&skey[(size_t)b * K + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         const double a1 = __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)&skey[(size_t)b * K + q + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        mx = fmax(mx, fabs(a1 - a0));
+        mx = nan_max(mx, fabs(a1 - a0));
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+    for (int o = 32; o > 0; o >>= 1) mx = nan_max(mx, __shfl_xor(mx, o, 64));
     if ((tid & 63) == 0) eb[tid >> 6] = mx;
     __syncthreads();
     if (tid == 0) {
-        mx = fmax(fmax(eb[0], eb[1]), fmax(eb[2], eb[3]));
+        mx = nan_max(nan_max(eb[0], eb[1]), nan_max(eb[2], eb[3]));
         if (mx < 10e-3) active[b] = 0;
         done[b] = 0;                                                          // ready for the next launch (stream order)
     }
@@ -286,17 +294,29 @@ __global__ void __launch_bounds__(256) k_sortperm_rank_big(const double* __restr
 
 // order = sortperm(cost) per slot, and (m_elite >= 2) the elite early-break check on the sorted costs.
 // skey ([B][K] doubles) / done ([B] ints, zero between launches): workspace of the chip-wide rank sort (nullptr: never used)
-void launch_sortperm(const double* cost, int32_t* order, int B, int K, int m_elite, int* active, hipStream_t s, double* skey, int* done) {
-    if (K <= 256) { hipLaunchKernelGGL(k_sortperm_rank, dim3(B), dim3(256), 0, s, cost, order, K, m_elite, active); return; }
+bool sortperm_multi_enabled() {
     static const int env_rm = [] { const char* e = getenv("MPOPIS_SORT_MULTI"); return e ? atoi(e) : 1; }();       // 0: bitonic only (A/B)
+    return env_rm != 0;
+}
+SortForm sortperm_form(int B, int K, bool have_ws, bool multi_enabled) {
+    if (K <= 256) return SORT_RANK;
     // measured, C4 (K = 4096): 49.5 -> 20.5 us per sort at one slot (step 5.97 -> 5.72 ms); at 8 slots 52 vs ~60 us, at 16 worse -- so: few slots only
-    if (env_rm && skey && done && K >= 2048 && (long long)B * K * K <= 2ll * 4096 * 4096) {
+    if (multi_enabled && have_ws && K >= 2048 && (long long)B * K * K <= 2ll * 4096 * 4096) return SORT_RANK_MULTI;
+    if (K > 8192) return SORT_RANK_BIG;                                     // beyond the one-workgroup bitonic network: chunked chip-wide rank sort, any K
+    if (K > 4096) return SORT_BITONIC8;                                     // n = 8192
+    if (K > 1024) return SORT_BITONIC4;                                     // n = 2048, 4096
+    return SORT_LDS;                                                        // n = 512, 1024
+}
+void launch_sortperm(const double* cost, int32_t* order, int B, int K, int m_elite, int* active, hipStream_t s, double* skey, int* done) {
+    const SortForm form = sortperm_form(B, K, skey && done, sortperm_multi_enabled());
+    if (form == SORT_RANK) { hipLaunchKernelGGL(k_sortperm_rank, dim3(B), dim3(256), 0, s, cost, order, K, m_elite, active); return; }
+    if (form == SORT_RANK_MULTI) {
         static std::atomic<unsigned long long> seenm{0};
         ensure_dyn_lds((const void*)k_sortperm_rank_multi, 96 * 1024, seenm);
         hipLaunchKernelGGL(k_sortperm_rank_multi, dim3((K + kRmE - 1) / kRmE, B), dim3(256), (size_t)K * sizeof(double), s, cost, order, K, m_elite, active, skey, done);
         return;
     }
-    if (K > 8192) {                                                         // beyond the one-workgroup bitonic network: chunked chip-wide rank sort, any K
+    if (form == SORT_RANK_BIG) {
         hipLaunchKernelGGL(k_sortperm_rank_big, dim3((K + kRmE - 1) / kRmE, B), dim3(256), 0, s, cost, order, K, m_elite, active, skey, done);
         return;
     }
@@ -304,10 +324,10 @@ void launch_sortperm(const double* cost, int32_t* order, int B, int K, int m_eli
     while (n < K) n <<= 1;
     const size_t bytes = (size_t)n * (sizeof(double) + sizeof(int32_t));
     static std::atomic<unsigned long long> seen8{0};
-    if (n >= 8192) {
+    if (form == SORT_BITONIC8) {
         ensure_dyn_lds((const void*)k_sortperm<8>, 150 * 1024, seen8);
         hipLaunchKernelGGL(k_sortperm<8>, dim3(B), dim3(n / 8), bytes, s, cost, order, K, n, m_elite, active);
-    } else if (n >= 2048) hipLaunchKernelGGL(k_sortperm<4>, dim3(B), dim3(n / 4), bytes, s, cost, order, K, n, m_elite, active);
+    } else if (form == SORT_BITONIC4) hipLaunchKernelGGL(k_sortperm<4>, dim3(B), dim3(n / 4), bytes, s, cost, order, K, n, m_elite, active);
     else hipLaunchKernelGGL(k_sortperm_lds, dim3(B), dim3(n / 2), bytes, s, cost, order, K, n, m_elite, active);
 }
 
@@ -522,15 +542,23 @@ __global__ void __launch_bounds__(kAliasParThreads) k_alias_build_par(const doub
 
 // need_ws (nullable): B ints of workspace; with it the parallel construction runs first and the sequential kernel only redoes the slots
 // that the parallel one could not certify
+bool alias_par_enabled() {
+    static const int env_par = [] { const char* e = getenv("MPOPIS_ALIAS_PAR"); return e ? atoi(e) : 1; }();
+    return env_par != 0;
+}
+AliasForm alias_build_form(int K, bool have_need_ws, bool par_enabled) {
+    if (K > kAliasLdsMaxK) return ALIAS_SEQ_GLOBAL;             // beyond what LDS holds: the sequential construction on global arrays (stack_ws: B x 2K ints)
+    return (have_need_ws && par_enabled && K <= 8192) ? ALIAS_PAR_THEN_SEQ_LDS : ALIAS_SEQ_LDS;
+}
 void launch_alias_build(const double* w, double* accept, int32_t* alias, int B, int K, const int* active, hipStream_t s, int* need_ws, int32_t* stack_ws) {
     const size_t bytes = (size_t)K * (8 + 4 + 4 + 4);
     static std::atomic<unsigned long long> seen{0}, seenp{0};
-    static const int env_par = [] { const char* e = getenv("MPOPIS_ALIAS_PAR"); return e ? atoi(e) : 1; }();
-    if (K > kAliasLdsMaxK) {                                    // beyond what LDS holds: the sequential construction on global arrays (stack_ws: B x 2K ints)
+    const AliasForm form = alias_build_form(K, need_ws != nullptr, alias_par_enabled());
+    if (form == ALIAS_SEQ_GLOBAL) {
         hipLaunchKernelGGL(k_alias_build<true>, dim3(B), dim3(64), 0, s, w, accept, alias, K, active, (const int*)nullptr, stack_ws);
         return;
     }
-    const bool par = need_ws && env_par && K <= 8192;
+    const bool par = form == ALIAS_PAR_THEN_SEQ_LDS;
     if (par) {
         ensure_dyn_lds((const void*)k_alias_build_par, 150 * 1024, seenp);
         hipLaunchKernelGGL(k_alias_build_par, dim3(B), dim3(kAliasParThreads), (size_t)K * 12, s, w, accept, alias, K, active, need_ws);
