@@ -754,10 +754,12 @@ int mpopis_bench_policy_steps(mpopis_handle* h, int32_t steps, double* ms, doubl
     HIPCHK(h, hipMemsetAsync(h->d_iters, 0, sizeof(int) * h->B, h->stream));
     HIPCHK(h, wait_stream(h->stream));
     HIPCHK(h, hipEventRecord(e0, h->stream));
+    h->chains_fork();                                           // the parts are forked once and joined once: a part's steps follow each other on its stream
     for (int s = 0; s < steps; ++s) {
-        int rc = h->policy_step_enqueue(false);
-        if (rc) return rc;
+        int rc = h->chains_step(false);
+        if (rc) { h->chains_join(); return rc; }
     }
+    h->chains_join();
     HIPCHK(h, hipEventRecord(e1, h->stream));
     HIPCHK(h, hipEventSynchronize(e1));
     float t = 0.f;
@@ -815,10 +817,10 @@ void mpopis_handle::shift_slots(ptrdiff_t db) {
     mv(d_lanV, (ptrdiff_t)invsqrt_workspace_doubles(1, cs, lan_regions)); mv(d_lan_x, (ptrdiff_t)invsqrt_coop_words(1, cs)); mv(d_Cdw, cs); mv(d_fro_part, (cs + 15) / 16); mv(d_tri_dinv, (ptrdiff_t)trtri_dinv_doubles(1, cs)); mv(d_fro, 1); mv(d_lan_m, 1); mv(d_lan_prep, (ptrdiff_t)lanczos_prep_doubles(1)); mv(d_tri_cnt, 2);
     mv(d_coop_flags, (ptrdiff_t)potrf_coop_flag_words(1, cs)); mv(d_potrf_redo, 1); mv(d_lan_redo, 1);
     mv(d_nesS, nn); mv(d_nesA[0], nn); mv(d_nesA[1], nn); mv(d_nesM, nn); mv(d_nesg, cs); mv(d_nesC, 1); mv(d_nespart, (ptrdiff_t)nes_scatter_workspace_doubles(1, cs, ksplit));
-    mv(alive_gate, 1);
+    mv(alive_gate, 1); mv(d_hs, kHarnessDoubles); mv(d_alive, 1); mv(d_actlog, actlog_stride);
 }
 
-// pol(env) for all slots.  Opt-in (mpopis_set_overlap): with >= 2 slots the batch is split into parts that run as independent chains on
+// pol(env) for all slots.  With >= 2 slots the batch may be split into parts that run as independent chains on
 // their own streams, each started one sampler later than the previous: while one part sits in a latency-bound link of its chain
 // (Cholesky: nb workgroups on 256 CUs; weights; the scatter's finish), the other half's rollout / sampler fills the chip.
 // Per-slot results are bit-identical to the single-stream order (every kernel is slot-independent and deterministic).
@@ -829,7 +831,9 @@ void mpopis_handle::shift_slots(ptrdiff_t db) {
 // Bit-identical per slot (every kernel is slot-independent and deterministic: tests/test_gpu_baseline_shapes.py).  The table is the
 // measured optimum (tools/split_sweep.py, one box, K = 4096 and 1024, 16..256 trials, ms per step at 1 / 2 / 3 / 4 parts), by rollout WAVES
 // in the batch (B x ceil(K / 64) for one car):
-//   :μΣaismppi  32 trials 3.37 / 4.07 / 3.80 / 4.24   48: 4.61 / 4.81 / 4.21 / 4.54   64: 5.72 / 5.75 / 5.63 / 5.36   96: 8.41 / 8.22 / 8.07 / 8.16   128: 10.7 all
+//   :μΣaismppi  32 trials 3.37 / 4.07 / 3.80 / 4.24   48: 4.67 / 4.72 / 4.02 / 4.36   64: 5.79 / 5.70 / 5.43 / 5.19   96: 8.30 / 8.03 / 7.81 / 7.83   128: 10.7 all
+//               (48 / 64 / 96 re-measured with the chains persisting across the steps of a call, see chains_fork; with a join after every step the same box gave
+//                4.67 / 4.80 / 4.12 / 4.48, 5.78 / 5.75 / 5.57 / 5.28 and 8.30 / 8.12 / 7.93 / 7.95: every multi-part schedule gains, the ranking does not move)
 //   :cemppi     32: 5.45 / 5.26 / 5.04 / 5.12        48: 7.02 / 6.09 / 5.51 / 5.56   64: 8.78 / 7.79 / 6.94 / 6.66   128: 15.4 / 13.9 / 13.2 / 12.9
 //   :pmcmppi    32: 4.69 / 5.46 / 4.71 / 5.28        48: 6.34 / 5.47 / 5.41 / 5.38   64: 7.93 / 6.95 / 6.78 / 6.77   128: 14.7 / 13.3 / 12.8 / 12.6
 //   :μaismppi   16: 2.30 / 2.04 / 2.29 / 2.44        32: 3.16 / 2.80 / 2.93 / 3.17   64: 4.96 / 4.37 / 4.57 / 4.49   128: 9.27 / 8.55 / 8.91 / 8.91
@@ -910,37 +914,73 @@ void mpopis_handle::verify_part_streams() {
     (void)hipGetLastError();
 }
 
-int mpopis_handle::policy_step_enqueue(bool injected) {
-    const int B0 = B;
-    int np = split_auto ? auto_parts() : std::min(nsplit, B0);
+// Part-chains outlive an MPC step.  Part p's step s + 1 needs nothing but part p's step s (every per-slot buffer is a shift_slots view, every shared
+// one is read-only), so a call that enqueues several steps -- mpopis_bench_policy_steps, run_trials -- forks the parts once (chains_fork), enqueues
+// step after step on each part's own stream (chains_step) and joins when the host next needs the whole batch (chains_join).  Joining after every step
+// drained the chip once per step: the last chain's final rollout alone at one wave per SIMD, then the latency-bound tail (weights, mean, finalize) and
+// head (step_begin, Σ0 broadcast) of the step with nothing beside them, and two cross-stream waits in between.
+// Skew: part p starts a step when part p-1 has left that step's first sampler.  MPOPIS_CHAIN_SKEW=1 keeps that one-directional edge at every step
+// (the default), 0 only at the first step after a fork (chains without any cross-edge may drift into phase: four parts in the same kernel is the
+// one-stream schedule); MPOPIS_CHAIN_JOIN=1 joins and re-forks after every step (the schedule before; A/B runs).  Numbers: DESIGN.md section 6.
+void mpopis_handle::chains_fork() {
+    int np = split_auto ? auto_parts() : std::min(nsplit, B);
     if (np >= 2 && !part_streams_checked) verify_part_streams();
-    np = std::min(np, max_parts);
+    chain_np = std::max(1, std::min(np, max_parts));
+    chain_fresh = true;
+    if (chain_np < 2) return;
+    (void)hipEventRecord(ev_fork, stream);                      // the other streams start after everything already queued on the main stream
+    for (int p = 1; p < chain_np; ++p) (void)hipStreamWaitEvent(xstream[p - 1], ev_fork, 0);
+}
+
+void mpopis_handle::chains_join() {
+    for (int p = 1; p < chain_np; ++p) {                        // later work on the main stream sees every part
+        (void)hipEventRecord(ev_join[p - 1], xstream[p - 1]);
+        (void)hipStreamWaitEvent(stream, ev_join[p - 1], 0);
+    }
+    chain_np = 0;
+}
+
+// one MPC step of every part of the open chain set; `tail` (nullable) is enqueued behind each part's step on that part's stream, with the handle
+// narrowed to that part's slots
+int mpopis_handle::chains_step(bool injected, const std::function<void()>& tail) {
+    static const int env_skew = [] { const char* e = getenv("MPOPIS_CHAIN_SKEW"); return e ? atoi(e) : 1; }();
+    static const int env_join = [] { const char* e = getenv("MPOPIS_CHAIN_JOIN"); return e ? atoi(e) : 0; }();
+    const int B0 = B, np = chain_np;
+    int rc = 0;
     if (np < 2) {
         side_free = (xstream[0] != nullptr);
-        const int rc = step_enqueue_view(injected, nullptr, nullptr);
+        rc = step_enqueue_view(injected, nullptr, nullptr);
         side_free = false;
-        mpc_step += 1;
-        if (!rc && !launch_err.empty()) { err = launch_err; launch_err.clear(); return MPOPIS_ERR_HIP; }
-        return rc;
+        if (!rc && tail) tail();
+    } else {
+        const bool skew = chain_fresh || env_skew;
+        hipStream_t main_stream = stream;
+        coop_share = np;                                        // up to np cluster launches in flight at once: each may take 1/np of the device
+        int b0 = 0;
+        for (int p = 0; p < np; ++p) {
+            const int nbp = B0 / np + (p < B0 % np ? 1 : 0);
+            if (p > 0) stream = xstream[p - 1];
+            B = nbp;
+            // part p starts when part p-1 has entered its first rollout (one sampler later) and tells part p+1 when it gets there itself
+            const int r = step_enqueue_view(injected, skew && p > 0 ? ev_skew[p - 1] : nullptr, skew && p + 1 < np ? ev_skew[p] : nullptr);
+            if (!rc) rc = r;
+            if (!r && tail) tail();
+            shift_slots(nbp); b0 += nbp;
+        }
+        shift_slots(-b0); B = B0; stream = main_stream; coop_share = 1;
     }
-    (void)hipEventRecord(ev_fork, stream);                      // the other streams start after everything already queued on the main stream
-    hipStream_t main_stream = stream;
-    coop_share = np;                                            // up to np cluster launches in flight at once: each may take 1/np of the device
-    int rc = 0, b0 = 0;
-    for (int p = 0; p < np; ++p) {
-        const int nbp = B0 / np + (p < B0 % np ? 1 : 0);
-        if (p > 0) { stream = xstream[p - 1]; (void)hipStreamWaitEvent(stream, ev_fork, 0); }
-        B = nbp;
-        // part p starts when part p-1 has entered its first rollout (one sampler later) and tells part p+1 when it gets there itself
-        const int r = step_enqueue_view(injected, p > 0 ? ev_skew[p - 1] : nullptr, p + 1 < np ? ev_skew[p] : nullptr);
-        if (!rc) rc = r;
-        if (p > 0) (void)hipEventRecord(ev_join[p - 1], stream);
-        shift_slots(nbp); b0 += nbp;
-    }
-    shift_slots(-b0); B = B0; stream = main_stream; coop_share = 1;
-    for (int p = 1; p < np; ++p) (void)hipStreamWaitEvent(stream, ev_join[p - 1], 0);   // later work on the main stream sees every part
+    chain_fresh = false;
     mpc_step += 1;
+    if (env_join && np >= 2) { chains_join(); chains_fork(); }
     if (!rc && !launch_err.empty()) { err = launch_err; launch_err.clear(); return MPOPIS_ERR_HIP; }
+    return rc;
+}
+
+// a single-step call: fork and join per call
+int mpopis_handle::policy_step_enqueue(bool injected) {
+    chains_fork();
+    const int rc = chains_step(injected);
+    chains_join();
     return rc;
 }
 

@@ -1,6 +1,7 @@
 // engine_handle.h -- the opaque handle behind include/mpopis.h (see engine.h for the HBM layout).
 #pragma once
 #include "engine.h"
+#include <functional>
 
 struct mpopis_handle {
     mpopis_config cfg{};
@@ -70,6 +71,8 @@ struct mpopis_handle {
     double *d_qdist = nullptr, *d_qbeta = nullptr; int* d_qwithin = nullptr;
     // Level-3 harness
     double* d_hs = nullptr; int* d_alive = nullptr; const int* alive_gate = nullptr; bool status_sticky = false;
+    static constexpr int kHarnessDoubles = 16;                 // per-slot accumulator of the trial loop (engine_harness.hip, kH_N)
+    double* d_actlog = nullptr; ptrdiff_t actlog_stride = 0;   // run_trials' action log of the current call ([B][num_steps + 1][as]) and its slot stride
     double noise_sx = 0.0, noise_sy = 0.0, noise_spsi = 0.0;   // simulate_car_racing state noise (car_example.jl:224-236)
     // RCCL communicator for the summary gather (engine_comm.hip); world == 1 needs none
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;
@@ -109,7 +112,13 @@ struct mpopis_handle {
     std::vector<hipStream_t> rejected_streams;            // (kept until the handle goes: destroying one would hand its queue to the next candidate)
     void verify_part_streams();
     int auto_parts() const;                               // part-chains of the default schedule for this handle's shape
-    int policy_step_enqueue(bool injected);
+    int policy_step_enqueue(bool injected);               // one MPC step of the whole batch: chains_fork + chains_step + chains_join
+    // Part-chains that outlive a step (engine_api.hip): fork the parts once, enqueue step after step on each part's own stream, join when the host
+    // needs the whole batch again.  chain_np: parts of the open set (0: none open); chain_fresh: no step enqueued since the fork.
+    int chain_np = 0; bool chain_fresh = false;
+    void chains_fork();
+    int chains_step(bool injected, const std::function<void()>& tail = {});
+    void chains_join();
     int step_enqueue_view(bool injected, hipEvent_t wait_first, hipEvent_t record_after_first_sampler);
     void shift_slots(ptrdiff_t db);                           // move every per-slot device pointer by db slots (slot views)
     int ais_update(int n, bool injected);

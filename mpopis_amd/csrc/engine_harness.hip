@@ -19,6 +19,7 @@ namespace mpopis {
 // per-slot accumulator (doubles): see kH_* indices
 enum { kH_rew = 0, kH_cnt, kH_lap, kH_prev_y, kH_trk, kH_beta, kH_crash, kH_vmean, kH_vmax, kH_bmean, kH_bmax,
        kH_lap0, kH_lap1, kH_lap2, kH_lap3, kH_rollouts, kH_N = 16 };
+static_assert(kH_N == mpopis_handle::kHarnessDoubles, "shift_slots moves d_hs by kHarnessDoubles per slot");
 
 __global__ void k_harness_init(double* hs, int* alive, int B) {
     const int b = blockIdx.x * 64 + threadIdx.x;
@@ -103,9 +104,11 @@ int mpopis_handle::run_trials(int num_steps, int laps, double* records, double* 
         if (hipMalloc((void**)&d_hs, sizeof(double) * kH_N * B) != hipSuccess || hipMalloc((void**)&d_alive, sizeof(int) * B) != hipSuccess) { err = "hipMalloc failed"; return MPOPIS_ERR_HIP; }
         allocs.push_back(d_hs); allocs.push_back(d_alive);
     }
-    double* d_actlog = nullptr;
+    // (d_actlog is a member for the length of this call: the part-chains log through their slot views of it)
+    struct ActlogGuard { mpopis_handle* h; ~ActlogGuard() { if (h->d_actlog) (void)hipFree(h->d_actlog); h->d_actlog = nullptr; h->actlog_stride = 0; } } actlog_guard{this};
     if (actions) {
-        if (hipMalloc((void**)&d_actlog, sizeof(double) * (size_t)B * (num_steps + 1) * as) != hipSuccess) { err = "hipMalloc failed"; return MPOPIS_ERR_HIP; }
+        if (hipMalloc((void**)&d_actlog, sizeof(double) * (size_t)B * (num_steps + 1) * as) != hipSuccess) { d_actlog = nullptr; err = "hipMalloc failed"; return MPOPIS_ERR_HIP; }
+        actlog_stride = (ptrdiff_t)(num_steps + 1) * as;
         (void)hipMemsetAsync(d_actlog, 0, sizeof(double) * (size_t)B * (num_steps + 1) * as, stream);
     }
     hipLaunchKernelGGL(k_harness_init, dim3((B + 63) / 64), dim3(64), 0, stream, d_hs, d_alive, B);
@@ -114,22 +117,27 @@ int mpopis_handle::run_trials(int num_steps, int laps, double* records, double* 
     status_sticky = true;                              // errors of any MPC step survive to the end of the call
     std::vector<int> h_alive(B, 1);
     int worst = 0;
+    const bool noisy = noise_sx != 0.0 || noise_sy != 0.0 || noise_spsi != 0.0;
     for (int s = 0; s <= num_steps; ++s) {
+        // The part-chains stay forked between the host's looks at the batch (every eighth step): a part's env step and bookkeeping follow its policy
+        // step on its own stream, on its own slots, and its next policy step follows them there.
+        if (!chain_np) chains_fork();
         alive_gate = d_alive;
-        int rc = policy_step_enqueue(false);
+        int rc = chains_step(false, [&] {                       // (runs once per part, with B / stream / the slot pointers narrowed to that part)
+            launch_env_step(env, d_x, d_t, d_done, d_control, d_reward, d_status, d_alive, B, stream);
+            hipLaunchKernelGGL(k_harness_update, dim3((B + 63) / 64), dim3(64), 0, stream, env, d_x, d_done, d_reward, d_iters, d_hs, d_alive,
+                               d_control, d_actlog, s, num_steps, laps, K, B,
+                               StateNoise{noise_sx, noise_sy, noise_spsi, noisy ? d_seeds : (const uint64_t*)nullptr, d_rng_tab});
+        });
         alive_gate = nullptr;
-        if (rc) { status_sticky = false; if (d_actlog) (void)hipFree(d_actlog); return rc; }
-        launch_env_step(env, d_x, d_t, d_done, d_control, d_reward, d_status, d_alive, B, stream);
-        const bool noisy = noise_sx != 0.0 || noise_sy != 0.0 || noise_spsi != 0.0;
-        hipLaunchKernelGGL(k_harness_update, dim3((B + 63) / 64), dim3(64), 0, stream, env, d_x, d_done, d_reward, d_iters, d_hs, d_alive,
-                           d_control, d_actlog, s, num_steps, laps, K, B,
-                           StateNoise{noise_sx, noise_sy, noise_spsi, noisy ? d_seeds : (const uint64_t*)nullptr, d_rng_tab});
+        if (rc) { chains_join(); status_sticky = false; return rc; }
         // error status is sticky per call of policy_step_enqueue (it clears d_status): fold it into the host view now and then
         if ((s & 7) == 7 || s == num_steps) {
+            chains_join();
             (void)hipMemcpyAsync(h_alive.data(), d_alive, sizeof(int) * B, hipMemcpyDeviceToHost, stream);
             (void)hipMemcpyAsync(h_status.data(), d_status, sizeof(int) * B, hipMemcpyDeviceToHost, stream);
             if (h_coop_timeouts && !coop_disabled) (void)hipMemcpyAsync(h_coop_timeouts, d_coop_timeouts, sizeof(int), hipMemcpyDeviceToHost, stream);
-            if (hipStreamSynchronize(stream) != hipSuccess) { err = "stream sync failed"; if (d_actlog) (void)hipFree(d_actlog); return MPOPIS_ERR_HIP; }
+            if (hipStreamSynchronize(stream) != hipSuccess) { err = "stream sync failed"; return MPOPIS_ERR_HIP; }
             if (h_coop_timeouts && *h_coop_timeouts > 0) coop_disabled = true;   // a cluster gave up (and was redone): stop using clusters, also within this call
             for (int b = 0; b < B; ++b) worst = mpopis::worse_status(worst, h_status[b]);
             bool any = false;
@@ -142,7 +150,6 @@ int mpopis_handle::run_trials(int num_steps, int laps, double* records, double* 
     if (hipMemcpyAsync(hs.data(), d_hs, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, stream) != hipSuccess) { err = "copy failed"; return MPOPIS_ERR_HIP; }
     if (actions) (void)hipMemcpyAsync(actions, d_actlog, sizeof(double) * (size_t)B * (num_steps + 1) * as, hipMemcpyDeviceToHost, stream);
     if (hipStreamSynchronize(stream) != hipSuccess) { err = "stream sync failed"; return MPOPIS_ERR_HIP; }
-    if (d_actlog) (void)hipFree(d_actlog);
     for (int b = 0; b < B; ++b) {                      // car_example.jl:287-302
         const double* h = hs.data() + (size_t)b * kH_N;
         double* r = records + (size_t)b * MPOPIS_RECORD_LEN;
