@@ -206,6 +206,12 @@ void launch_wcov_mfma(const double* X, const double* w, const int32_t* idx, int 
                       const double* rscale = nullptr, double* mu_out = nullptr, double* u_add = nullptr, const double* wsum = nullptr,
                       const double* cost = nullptr, unsigned long long* cmin = nullptr, double neg_inv_lambda = 0.0, const double* mu_shift = nullptr);
 bool wcov_weights_from_cost_ok(int cs, int K, int ksplit);
+// which partial kernel launch_wcov_mfma runs (pair list with 64- / 16-column chunks, the 8-wave row form, the 8-wave tall form), whether it stages the
+// fourth-moment rows (sq), the ones row (aug: the pass also yields μ) and the weights from the costs; MPOPIS_WCOV_ROWS is read once per process
+enum WcovPartial { WCOV_PAIR64 = 0, WCOV_PAIR16 = 1, WCOV_ROWS = 2, WCOV_TALL = 3 };
+struct WcovForm { WcovPartial partial; bool sq, aug, from_cost; };
+int wcov_rows_env();
+WcovForm wcov_form(int cs, int K, int m, int ksplit, int batch /* > 0, or -1: compact form */, bool has_rscale, bool has_idx, bool wants_mean, bool has_cost);
 bool wcov_mfma_can_emit_mean(int cs);
 void launch_inv_sd(const double* S, double* rs, int B, int cs, const int* active, hipStream_t s);
 void launch_common_shrink(double* S, int B, int cs, int m, int oas, double ridge, const int* active, hipStream_t s);
@@ -224,6 +230,11 @@ bool ce_cov_small_ok(int cs, int m, int est);
 bool ce_sort_fusable(int K);
 void launch_ce_cov_small(const double* E, int32_t* order, double* mu, double* S, double* Ucur, int B, int cs, int K, int m, int est, double ridge,
                          int* active, hipStream_t s, const double* cost = nullptr /* non-null (K <= 256): also sortperm(cost) -> order and the elite early break */);
+// engine_ais.hip: the same update for any elite set, as the sequence gather-mean, scatter (twice for :ss / :lw), shrinkage, and -- in a call of its
+// own, which the handle times apart -- pol.U += μ′ (d_gvec is free as rs there: γ's row is rebuilt per iteration)
+void launch_ce_cov_general(const double* E, const int32_t* order, double* mu, double* Sig, double* tmpS, double* rs, double* part,
+                           int B, int cs, int K, int m_elite, int ksplit, int sel_batch, int est, double ridge, const int* active, hipStream_t s);
+void launch_add_active(const double* x, double* y, int B, int n, const int* active, hipStream_t s);      // y[b] += x[b] for active slots
 
 // kernels_select.hip
 void launch_sortperm(const double* cost, int32_t* order, int B, int K, int m_elite, int* active, hipStream_t s,

@@ -58,6 +58,32 @@ void mpopis_handle::init_cma_constants() {
 void mpopis_handle::cma_begin() { launch_cma_begin(d_cma_scal, d_cma_vec, d_sig2, cfg.cma_sigma, cs, B, stream); }
 const double* mpopis_handle::cma_sigma2() { return d_sig2; }
 
+namespace mpopis {
+// The CE proposal update for elite sets the one-launch kernel (kernels_ce.hip) does not take: μ′ = mean of the elite columns E[:, order[0..m)],
+// Σ′ = cov(Σ_est, elite') + ridge I (:464) by the scatter kernels and the shrinkage kernel of the estimator; launch_add_active(mu, Ucur) completes it.
+// tmpS [B][cs][cs] (the fourth-moment scatter of :ss / :lw) and rs [B][cs] are workspace.
+void launch_ce_cov_general(const double* E, const int32_t* order, double* mu, double* Sig, double* tmpS, double* rs, double* part,
+                           int B, int cs, int K, int m_elite, int ksplit, int sel_batch, int est, double ridge, const int* active, hipStream_t stream) {
+    launch_gather_mean(E, order, nullptr, mu, B, cs, K, m_elite, 1, active, stream);
+    if (est == MPOPIS_SIGMA_EST_RBLW || est == MPOPIS_SIGMA_EST_OAS) {   // DiagonalCommonVariance :421-423
+        launch_wcov_mfma(E, nullptr, order, m_elite, mu, Sig, part, B, cs, K, ksplit, sel_batch, (double)m_elite, 0.0, active, stream);
+        launch_common_shrink(Sig, B, cs, m_elite, est == MPOPIS_SIGMA_EST_OAS, ridge, active, stream);
+    } else if (est == MPOPIS_SIGMA_EST_SS || est == MPOPIS_SIGMA_EST_LW) {   // DiagonalUnequalVariance :417-419
+        launch_wcov_mfma(E, nullptr, order, m_elite, mu, Sig, part, B, cs, K, ksplit, sel_batch, (double)m_elite, 0.0, active, stream);
+        if (est == MPOPIS_SIGMA_EST_SS) launch_inv_sd(Sig, rs, B, cs, active, stream);
+        else launch_fill_f64(rs, 1.0, (size_t)B * cs, stream);                       // :lw = same intensity on the unstandardised data
+        launch_wcov_mfma(E, nullptr, order, m_elite, mu, tmpS, part, B, cs, K, ksplit, sel_batch, 1.0, 0.0, active, stream, rs);
+        launch_ss_shrink(Sig, tmpS, rs, B, cs, m_elite, ridge, active, stream);
+    } else {
+        launch_wcov_mfma(E, nullptr, order, m_elite, mu, Sig, part, B, cs, K, ksplit, sel_batch, (double)m_elite, ridge, active, stream);
+    }
+}
+// pol.U += μ′ (:465): the last link of the sequence, launched by the caller behind its own timing bracket
+void launch_add_active(const double* x, double* y, int B, int n, const int* active, hipStream_t stream) {
+    hipLaunchKernelGGL(k_add_active, dim3((n + 255) / 256, B), dim3(256), 0, stream, x, y, n, active);
+}
+}  // namespace mpopis
+
 int mpopis_handle::ais_update(int n, bool injected) {
     const int pol = cfg.policy;
     if (pol == MPOPIS_POL_IMPPI || pol == MPOPIS_POL_MUAISMPPI || pol == MPOPIS_POL_MUSIGMAAISMPPI) {
@@ -144,21 +170,9 @@ int mpopis_handle::ais_update(int n, bool injected) {
                 return MPOPIS_OK;
             }
             time_begin(4);
-            launch_gather_mean(d_E, d_order, nullptr, d_mu, B, cs, K, m_elite, 1, d_active, stream);
-            if (cfg.sigma_est == MPOPIS_SIGMA_EST_RBLW || cfg.sigma_est == MPOPIS_SIGMA_EST_OAS) {   // DiagonalCommonVariance :421-423
-                launch_wcov_mfma(d_E, nullptr, d_order, m_elite, d_mu, d_Sig, d_part, B, cs, K, ksplit, wcov_sel_batch(), (double)m_elite, 0.0, d_active, stream);
-                launch_common_shrink(d_Sig, B, cs, m_elite, cfg.sigma_est == MPOPIS_SIGMA_EST_OAS, 10e-9, d_active, stream);
-            } else if (cfg.sigma_est == MPOPIS_SIGMA_EST_SS || cfg.sigma_est == MPOPIS_SIGMA_EST_LW) {   // DiagonalUnequalVariance :417-419
-                launch_wcov_mfma(d_E, nullptr, d_order, m_elite, d_mu, d_Sig, d_part, B, cs, K, ksplit, wcov_sel_batch(), (double)m_elite, 0.0, d_active, stream);
-                if (cfg.sigma_est == MPOPIS_SIGMA_EST_SS) launch_inv_sd(d_Sig, d_gvec, B, cs, d_active, stream);   // d_gvec is free here (γ row is rebuilt per iteration)
-                else launch_fill_f64(d_gvec, 1.0, (size_t)B * cs, stream);                       // :lw = same intensity on the unstandardised data
-                launch_wcov_mfma(d_E, nullptr, d_order, m_elite, d_mu, d_tmpS, d_part, B, cs, K, ksplit, wcov_sel_batch(), 1.0, 0.0, d_active, stream, d_gvec);
-                launch_ss_shrink(d_Sig, d_tmpS, d_gvec, B, cs, m_elite, 10e-9, d_active, stream);
-            } else {
-                launch_wcov_mfma(d_E, nullptr, d_order, m_elite, d_mu, d_Sig, d_part, B, cs, K, ksplit, wcov_sel_batch(), (double)m_elite, 10e-9, d_active, stream);
-            }
+            launch_ce_cov_general(d_E, d_order, d_mu, d_Sig, d_tmpS, d_gvec, d_part, B, cs, K, m_elite, ksplit, wcov_sel_batch(), cfg.sigma_est, 10e-9, d_active, stream);
             time_end();
-            hipLaunchKernelGGL(k_add_active, dim3((cs + 255) / 256, B), dim3(256), 0, stream, d_mu, d_Ucur, cs, d_active);
+            launch_add_active(d_mu, d_Ucur, B, cs, d_active, stream);
             return MPOPIS_OK;
         }
         time_begin(4);

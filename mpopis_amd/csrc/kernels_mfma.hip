@@ -589,24 +589,39 @@ size_t wcov_mfma_workspace_doubles(int B, int cs, int ksplit) {
     return (size_t)B * ksplit * (nt * (nt + 1) / 2) * 256;
 }
 bool wcov_mfma_can_emit_mean(int cs) { return (cs & 15) != 0; }      // needs a padding row for the ones
-void launch_wcov_mfma(const double* X, const double* w, const int32_t* idx, int m, const double* mu, double* S, double* part,
-                      int B, int cs, int K, int ksplit, int sel_batch, double den, double ridge, const int* active, hipStream_t s, const double* rscale,
-                      double* mu_out, double* u_add, const double* wsum, const double* cost, unsigned long long* cmin, double neg_inv_lambda,
-                      const double* mu_shift) {
-    const int aug = (mu_out && !rscale && wcov_mfma_can_emit_mean(cs)) ? 1 : 0;   // mu_out: also produce μ = Σ w x / Σw (mu is then unused)
-    const bool from_cost = cost && cmin && aug && !idx && wcov_weights_from_cost_ok(cs, K, ksplit);
-    if (!from_cost) { cost = nullptr; cmin = nullptr; }
-    const int nt = (cs + 15) / 16, npairs = nt * (nt + 1) / 2;
-    const int kc = wcov_kc(cs);
-    const int per = ((m + ksplit - 1) / ksplit + kc - 1) / kc * kc;
-    static const int env_rows = [] { const char* e = getenv("MPOPIS_WCOV_ROWS"); return e ? atoi(e) : 1; }();
+int wcov_rows_env() { static const int env_rows = [] { const char* e = getenv("MPOPIS_WCOV_ROWS"); return e ? atoi(e) : 1; }(); return env_rows; }
+// The partial kernel launch_wcov_mfma runs, and what it folds into the pass, as a pure function of the launch's shape (the launcher calls it;
+// tools/kbench_mfma.hip reports it, so that a test written for one form fails when a threshold moves).  batch: the batch the choice goes by
+// (the launcher's sel_batch, or its B when that is 0); -1: compact form.  m is part of the shape but no rule reads it today.
+WcovForm wcov_form(int cs, int K, int m, int ksplit, int batch, bool has_rscale, bool has_idx, bool wants_mean, bool has_cost) {
+    (void)m;
+    WcovForm f;
+    f.sq = has_rscale;
+    f.aug = wants_mean && !has_rscale && wcov_mfma_can_emit_mean(cs);
+    f.from_cost = has_cost && f.aug && !has_idx && wcov_weights_from_cost_ok(cs, K, ksplit);
+    const int nt = (cs + 15) / 16, env_rows = wcov_rows_env();
     // row form: 7 row tiles (kc == 64 then), an even number of partials, and enough 8-wave workgroups for most of the CUs (measured: wins from 16
     // resident C5 trials up -- 30 -> 28 us at 16, 86 -> 74 us at 64 -- and loses ~5 us at 8, where it fields 128 workgroups)
     // The choice goes by the handle's WHOLE batch (sel_batch), not by this launch's share of it: the part-chains of a multi-stream schedule are in
     // flight together, and a slot's result must not depend on the schedule (the two forms agree to rounding, not bit for bit).
-    const bool rows = env_rows && nt == 7 && !rscale && !(ksplit & 1) && sel_batch >= 0 && (long long)(sel_batch > 0 ? sel_batch : B) * (ksplit / 2) >= (env_rows > 1 ? 1 : 192);
+    const bool rows = env_rows && nt == 7 && !has_rscale && !(ksplit & 1) && batch >= 0 && (long long)batch * (ksplit / 2) >= (env_rows > 1 ? 1 : 192);
     // cs > 512 (six cars and more at H = 50): the 8-wave pair-list form, up to kWcovTallRows rows (mpopis_create refuses larger cs)
     const bool tall = nt * 16 > 512;
+    f.partial = tall ? WCOV_TALL : rows ? WCOV_ROWS : wcov_kc(cs) == 64 ? WCOV_PAIR64 : WCOV_PAIR16;
+    return f;
+}
+void launch_wcov_mfma(const double* X, const double* w, const int32_t* idx, int m, const double* mu, double* S, double* part,
+                      int B, int cs, int K, int ksplit, int sel_batch, double den, double ridge, const int* active, hipStream_t s, const double* rscale,
+                      double* mu_out, double* u_add, const double* wsum, const double* cost, unsigned long long* cmin, double neg_inv_lambda,
+                      const double* mu_shift) {
+    const WcovForm form = wcov_form(cs, K, m, ksplit, sel_batch == 0 ? B : sel_batch, rscale != nullptr, idx != nullptr, mu_out != nullptr, cost && cmin);
+    const int aug = form.aug ? 1 : 0;                           // mu_out: also produce μ = Σ w x / Σw (mu is then unused)
+    const bool from_cost = form.from_cost;
+    if (!from_cost) { cost = nullptr; cmin = nullptr; }
+    const int nt = (cs + 15) / 16, npairs = nt * (nt + 1) / 2;
+    const int kc = wcov_kc(cs);
+    const int per = ((m + ksplit - 1) / ksplit + kc - 1) / kc * kc;
+    const bool rows = form.partial == WCOV_ROWS, tall = form.partial == WCOV_TALL;
     const size_t lds = ((size_t)nt * 16 * (rows ? 2 * kRowsS : kc + 1) + kc + (from_cost ? (rows ? 2 * per : per) : 0)) * sizeof(double);
     static std::atomic<unsigned long long> seen[5];
     ensure_dyn_lds((const void*)k_wcov_mfma_partial<64, false, true>, 160 * 1024, seen[4]);
