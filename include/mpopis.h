@@ -50,7 +50,11 @@ extern "C" {
  *    policy = 8 with MPOPIS_ERR_ARG / "No policy_type of that kind", which is how a caller detects support.
  *    Later still, num_cars up to MPOPIS_MAX_CARS = 8 (was 4), and nothing else: a library that predates it answers num_cars = 5..8 with
  *    MPOPIS_ERR_ARG / "num_cars must be 1..4".  Since then :cemppi, :μΣaismppi and :pmcmppi refuse cs > 800 at create (MPOPIS_ERR_ARG): their
- *    covariance scatter stages at most 800 rows, and earlier libraries returned a wrong Σ′ there (past 512 rows) instead of refusing. */
+ *    covariance scatter stages at most 800 rows, and earlier libraries returned a wrong Σ′ there (past 512 rows) instead of refusing.
+ *    Later gained the env kind MPOPIS_ENV_CUSTOM = 3 and ONE entry point, mpopis_create_custom (a handle on a caller-supplied env compiled to a
+ *    gfx950 code object, include/mpopis_env.h); mpopis_config and every other entry point are unchanged.  A library that predates it does not
+ *    export the symbol, which is how a caller detects support (env_kind = 3 was "unknown env kind" to mpopis_create before and is still refused
+ *    there, now with a message that names the new entry point). */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -58,7 +62,8 @@ enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_AC
 /* env kinds: RL.jl MountainCarEnv(continuous=true) + src/examples/mountaincar_example.jl:4-22;
  * CarRacingEnv src/envs/car_racing.jl (num_cars==1) / MultiCarRacingEnv src/envs/multi-car_racing.jl;
  * RL.jl CartPoleEnv(continuous=true) + src/examples/cartpole_example.jl:3-6 (state [x,xdot,theta,thetadot]) */
-enum { MPOPIS_ENV_MOUNTAINCAR = 0, MPOPIS_ENV_CAR = 1, MPOPIS_ENV_CARTPOLE = 2 };
+enum { MPOPIS_ENV_MOUNTAINCAR = 0, MPOPIS_ENV_CAR = 1, MPOPIS_ENV_CARTPOLE = 2,
+       MPOPIS_ENV_CUSTOM = 3 };      /* any env written against include/mpopis_env.h: only through mpopis_create_custom */
 /* largest num_cars of the car env (MultiCarRacingEnv(N) takes any N in the reference) */
 #define MPOPIS_MAX_CARS 8
 
@@ -128,6 +133,22 @@ const char *mpopis_last_error(const mpopis_handle *h);     /* h may be NULL: las
  * src/examples/car_example.jl:172-185.  Defaults after create: env params = reference
  * defaults, track = none (must be set for car envs), bounds = [-1,1], U = 0, Sigma = I. */
 int  mpopis_create(const mpopis_config *cfg, mpopis_handle **out);
+/* XPolicy(env; kwargs...) for ANY env: the reference runs every policy on every AbstractEnv that has env(a), reward(env), state(env) and
+ * action_space(env) (rollout_model(env::AbstractEnv, ...) src/utils.jl:129-144; simulate_model(pol, env::AbstractEnv, ...)
+ * src/mppi_mpopi_policies.jl:261-278).  Here env(a) and reward(env) are two device functions compiled with include/mpopis_env.h into a
+ * gfx950 code object (hipcc --genco); the engine loads it and launches its kernels where it launches its own rollout / env-step kernels.
+ *   cfg            as for mpopis_create; env_kind and num_cars are ignored (the handle's env kind is MPOPIS_ENV_CUSTOM)
+ *   code_object    nbytes bytes: the ELF or clang offload bundle hipcc wrote; copied by the runtime, not retained
+ *   state_size 1..64, action_size 1..16, nparams 0..64: must equal what the code object was built with (cs = action_size H obeys the
+ *                  per-policy limits listed at mpopis_config.num_cars)
+ *   reset_state    state_size doubles that mpopis_reset restores in every slot (with t = 0, done = 0), or NULL for zeros
+ * On such a handle mpopis_set_env_params takes exactly nparams doubles (default: zeros), mpopis_set_action_bounds holds per action
+ * (default [-1, 1]), mpopis_env_query returns reward(env) and within = 1, mpopis_run_trials ends a slot when the env sets done, and
+ * mpopis_set_track / mpopis_set_state_noise have no effect; everything else works as on a built-in env.  The module is unloaded by
+ * mpopis_destroy; handles with different code objects coexist. */
+int  mpopis_create_custom(const mpopis_config *cfg, const void *code_object, uint64_t nbytes,
+                          int32_t state_size, int32_t action_size, int32_t nparams,
+                          const double *reset_state /* state_size doubles or NULL => zeros */, mpopis_handle **out);
 void mpopis_destroy(mpopis_handle *h);
 
 /* ---- env description (the env protocol the path consumes) ------------------------ */

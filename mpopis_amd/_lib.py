@@ -12,8 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # at a variant build instead of overwriting the product binary.
 LIB_PATH = os.environ.get("MPOPIS_HIP_LIB") or os.path.join(_HERE, "lib", "libmpopis_hip.so")
 
-ENV_MOUNTAINCAR, ENV_CAR, ENV_CARTPOLE = 0, 1, 2
-ENV_IDS = {"mountaincar": ENV_MOUNTAINCAR, "car": ENV_CAR, "cartpole": ENV_CARTPOLE}
+ENV_MOUNTAINCAR, ENV_CAR, ENV_CARTPOLE, ENV_CUSTOM = 0, 1, 2, 3
+ENV_IDS = {"mountaincar": ENV_MOUNTAINCAR, "car": ENV_CAR, "cartpole": ENV_CARTPOLE, "custom": ENV_CUSTOM}
 POLICY_IDS = {"mppi": 0, "gmppi": 1, "imppi": 2, "cemppi": 3, "cmamppi": 4,
               "μaismppi": 5, "muaismppi": 5, "μΣaismppi": 6, "musigmaaismppi": 6, "pmcmppi": 7,
               "nesmppi": 8}
@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "mpopis_seed", "mpopis_seed_slots", "mpopis_get_Sigma", "mpopis_rollout_costs", "mpopis_policy_step", "mpopis_env_step",
     "mpopis_env_query", "mpopis_get_trajectories", "mpopis_set_state_noise", "mpopis_run_trials", "mpopis_timing_enable", "mpopis_timing_read",
     "mpopis_timing_reset", "mpopis_bench_policy_steps",
-    "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
+    "mpopis_create_custom", "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
 ]
 
 
@@ -69,6 +69,8 @@ def lib():
         L.mpopis_last_error.restype = C.c_char_p
         L.mpopis_last_error.argtypes = [H]
         L.mpopis_create.argtypes = [C.POINTER(Config), C.POINTER(H)]
+        if hasattr(L, "mpopis_create_custom"):                  # (a MPOPIS_HIP_LIB build that predates custom envs still serves the built-in ones)
+            L.mpopis_create_custom.argtypes = [C.POINTER(Config), C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(H)]
         L.mpopis_destroy.argtypes = [H]
         L.mpopis_destroy.restype = None
         L.mpopis_set_env_params.argtypes = [H, _dp, C.c_int32]

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "../../include/mpopis.h"
+#include "../../include/mpopis_env.h"
 #include "car_dynamics.h"
 
 namespace mpopis {
@@ -43,6 +44,16 @@ inline void ensure_dyn_lds(const void* fn, int bytes, std::atomic<unsigned long 
 
 constexpr int kMaxCars = MPOPIS_MAX_CARS;      // include/mpopis.h; the rollout kernels are instantiated for 1..8 cars
 constexpr int kMaxAs = 2 * kMaxCars;
+static_assert(kMaxAs == MPOPIS_ENV_MAX_ACTION && MPOPIS_ENV_ERR_ACTION == MPOPIS_ERR_ACTION, "include/mpopis_env.h restates these");
+
+// A caller-supplied env (MPOPIS_ENV_CUSTOM, include/mpopis_env.h): the loaded code object, its three kernels and the device parameter
+// buffer.  Owned by the handle; the launchers below reach it through EnvDesc::custom (a HOST pointer: kernels never look at it).
+struct CustomEnv {
+    hipModule_t module = nullptr;
+    hipFunction_t rollout = nullptr, step = nullptr, query = nullptr;
+    double* d_params = nullptr;
+    int nparams = 0;
+};
 
 struct EnvDesc {
     int kind;        // MPOPIS_ENV_*
@@ -53,6 +64,7 @@ struct EnvDesc {
     CpParams cp;
     Track track;     // device pointers
     double lo[kMaxAs], hi[kMaxAs];
+    const CustomEnv* custom;   // MPOPIS_ENV_CUSTOM only
 };
 
 // the two scalar-action classic-control envs share one code path ("simple" envs): ss = 2 or 4, as = 1
@@ -111,7 +123,7 @@ __device__ __forceinline__ void status_raise(int* p, int code) {
     }
 }
 
-bool launch_rollout(const RolloutArgs& a, hipStream_t s);      // false: no rollout kernel for this env (nothing launched)
+bool launch_rollout(const RolloutArgs& a, hipStream_t s, hipError_t* custom_err = nullptr);      // false: nothing launched -- no rollout kernel for this env, or the custom env's launch failed (*custom_err says why)
 void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t s, const Track& tk);
 // (iters_acc: per-slot running sum of the iteration counts of earlier steps, folded in before iters is cleared; may be null)
 void launch_step_begin(int* status, int* active, const int* alive, int* iters, const double* U, double* Uin, double* Ucur, int B, int cs,
@@ -139,10 +151,11 @@ void launch_transpose_out(const double* src_rows, const double* shiftA, const do
                           double* dst_colmajor, int B, int cs, int K, hipStream_t s);
 
 // real env step + reward for the resident envs
-void launch_env_step(const EnvDesc& env, double* x, int* t, int* done, const double* action,
-                     double* reward, int* status, const int* alive, int B, hipStream_t s);
+// (both return the launch status of a custom env's kernel; hipSuccess for the built-in envs, whose launches show in hipGetLastError)
+hipError_t launch_env_step(const EnvDesc& env, double* x, int* t, int* done, const double* action,
+                           double* reward, int* status, const int* alive, int B, hipStream_t s);
 
-void launch_env_query(const EnvDesc& env, const double* x, const int* done, double* reward, int* within, double* dist, double* beta, int B, hipStream_t s);
+hipError_t launch_env_query(const EnvDesc& env, const double* x, const int* t, const int* done, double* reward, int* within, double* dist, double* beta, int B, hipStream_t s);
 
 // kernels_sample.hip
 void launch_sample_normal(double* Z, int B, int cs, int K, int as, int mppi_order, const uint64_t* seeds,

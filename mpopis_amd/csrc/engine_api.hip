@@ -172,27 +172,127 @@ static void default_cp_params(double* p) {       // RL.jl CartPoleEnvParams
     memcpy(p, v, sizeof v);
 }
 
-int mpopis_create(const mpopis_config* cfg, mpopis_handle** out) {
-    if (!cfg || !out) { g_create_error = "null argument"; return MPOPIS_ERR_ARG; }
-    *out = nullptr;
-    const bool car = cfg->env_kind == MPOPIS_ENV_CAR;
-    if (!(car || cfg->env_kind == MPOPIS_ENV_MOUNTAINCAR || cfg->env_kind == MPOPIS_ENV_CARTPOLE)) { g_create_error = "unknown env kind"; return MPOPIS_ERR_ARG; }
-    if (car && (cfg->num_cars < 1 || cfg->num_cars > kMaxCars)) { g_create_error = "num_cars must be 1..8"; return MPOPIS_ERR_ARG; }
-    static_assert(kMaxCars == 8, "the message above names the bound");
+// The checks every create call makes before it touches the device: policy, shape, and the per-policy limits on cs = as * H.
+static int check_policy_config(const mpopis_config* cfg, int as) {
     if (cfg->policy < MPOPIS_POL_MPPI || cfg->policy > MPOPIS_POL_NESMPPI) { g_create_error = "No policy_type of that kind"; return MPOPIS_ERR_ARG; }
     if (cfg->num_samples < 1 || cfg->horizon < 1 || cfg->batch < 1) { g_create_error = "num_samples, horizon, batch must be >= 1"; return MPOPIS_ERR_ARG; }
     if (cfg->policy == MPOPIS_POL_NESMPPI) {
         // K = 1: maximum(abs.(diff(cost))) of an empty diff throws in the reference (src/mppi_mpopi_policies.jl:868)
         if (cfg->num_samples < 2) { g_create_error = "nesmppi: num_samples must be >= 2 (the early-break test takes diff(cost))"; return MPOPIS_ERR_ARG; }
-        if ((car ? 2 * cfg->num_cars : 1) * cfg->horizon > 512) { g_create_error = "nesmppi: control space too large (cs <= 512, the range of the dense Σ′ scatter)"; return MPOPIS_ERR_ARG; }
+        if ((long long)as * cfg->horizon > 512) { g_create_error = "nesmppi: control space too large (cs <= 512, the range of the dense Σ′ scatter)"; return MPOPIS_ERR_ARG; }
         if (!std::isfinite(cfg->cma_sigma)) { g_create_error = "nesmppi: step_factor (cma_sigma) must be finite"; return MPOPIS_ERR_ARG; }
     }
-    if (cfg->policy == MPOPIS_POL_CMAMPPI && (car ? 2 * cfg->num_cars : 1) * cfg->horizon > invsqrt_max_n()) { g_create_error = "cmamppi: control space too large for the on-chip Σ^-0.5 δw kernel"; return MPOPIS_ERR_ARG; }
+    if (cfg->policy == MPOPIS_POL_CMAMPPI && (long long)as * cfg->horizon > invsqrt_max_n()) { g_create_error = "cmamppi: control space too large for the on-chip Σ^-0.5 δw kernel"; return MPOPIS_ERR_ARG; }
     if ((cfg->policy == MPOPIS_POL_CEMPPI || cfg->policy == MPOPIS_POL_MUSIGMAAISMPPI || cfg->policy == MPOPIS_POL_PMCMPPI) &&
-        (long long)(car ? 2 * cfg->num_cars : 1) * cfg->horizon > wcov_max_cs()) {
+        (long long)as * cfg->horizon > wcov_max_cs()) {
         static const std::string msg = "control space too large for the covariance scatter of :cemppi / :μΣaismppi / :pmcmppi (cs <= " + std::to_string(wcov_max_cs()) + ")";
         g_create_error = msg; return MPOPIS_ERR_ARG;
     }
+    return MPOPIS_OK;
+}
+
+static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle** out);
+
+// hipModuleLoadData takes no length: a buffer whose own tables point past nbytes would be read beyond the caller's memory.  Little-endian ELF64
+// (the section header table and, through it, every section must lie inside) or a clang offload bundle (every entry must; an ELF entry is checked too).
+static bool code_object_complete(const unsigned char* p, uint64_t n) {
+    auto rd = [p](uint64_t off, int bytes) { uint64_t v = 0; for (int i = bytes - 1; i >= 0; --i) v = (v << 8) | p[off + i]; return v; };
+    auto inside = [n](uint64_t off, uint64_t len) { return off <= n && len <= n - off; };
+    if (n >= 64 && memcmp(p, "\x7f" "ELF", 4) == 0) {
+        const uint64_t shoff = rd(0x28, 8), shentsize = rd(0x3A, 2), shnum = rd(0x3C, 2);
+        if (shnum == 0) return true;
+        if (shentsize < 64 || !inside(shoff, shentsize * shnum)) return false;
+        for (uint64_t i = 0; i < shnum; ++i) {
+            const uint64_t sh = shoff + i * shentsize;
+            if (rd(sh + 4, 4) != 8 /* SHT_NOBITS occupies no file bytes */ && !inside(rd(sh + 0x18, 8), rd(sh + 0x20, 8))) return false;
+        }
+        return true;
+    }
+    uint64_t pos = 24;                                                         // behind the magic: entry count, then {offset, size, triple length, triple} per entry
+    if (!inside(pos, 8)) return false;
+    const uint64_t entries = rd(pos, 8); pos += 8;
+    for (uint64_t i = 0; i < entries; ++i) {
+        if (!inside(pos, 24)) return false;
+        const uint64_t off = rd(pos, 8), size = rd(pos + 8, 8), tl = rd(pos + 16, 8);
+        pos += 24;
+        if (!inside(pos, tl) || !inside(off, size)) return false;
+        pos += tl;
+        if (size >= 64 && memcmp(p + off, "\x7f" "ELF", 4) == 0 && !code_object_complete(p + off, size)) return false;
+    }
+    return true;
+}
+
+int mpopis_create(const mpopis_config* cfg, mpopis_handle** out) {
+    if (!cfg || !out) { g_create_error = "null argument"; return MPOPIS_ERR_ARG; }
+    *out = nullptr;
+    const bool car = cfg->env_kind == MPOPIS_ENV_CAR;
+    if (cfg->env_kind == MPOPIS_ENV_CUSTOM) { g_create_error = "env kind MPOPIS_ENV_CUSTOM needs a code object: create the handle with mpopis_create_custom"; return MPOPIS_ERR_ARG; }
+    if (!(car || cfg->env_kind == MPOPIS_ENV_MOUNTAINCAR || cfg->env_kind == MPOPIS_ENV_CARTPOLE)) { g_create_error = "unknown env kind"; return MPOPIS_ERR_ARG; }
+    if (car && (cfg->num_cars < 1 || cfg->num_cars > kMaxCars)) { g_create_error = "num_cars must be 1..8"; return MPOPIS_ERR_ARG; }
+    static_assert(kMaxCars == 8, "the message above names the bound");
+    const int as = car ? 2 * cfg->num_cars : 1;
+    if (const int rc = check_policy_config(cfg, as)) return rc;
+    return create_handle(cfg, as, car ? 8 * cfg->num_cars : (cfg->env_kind == MPOPIS_ENV_CARTPOLE ? 4 : 2), out);
+}
+
+// A handle on a caller-supplied env (include/mpopis_env.h).  Every argument check comes before the first HIP call.
+int mpopis_create_custom(const mpopis_config* cfg_in, const void* code_object, uint64_t nbytes, int32_t state_size, int32_t action_size, int32_t nparams,
+                         const double* reset_state, mpopis_handle** out) {
+    if (!cfg_in || !code_object || !out) { g_create_error = "null argument"; return MPOPIS_ERR_ARG; }
+    *out = nullptr;
+    static const char kElf[4] = {0x7f, 'E', 'L', 'F'}, kBundle[] = "__CLANG_OFFLOAD_BUNDLE__";
+    if (nbytes < 64) { g_create_error = "mpopis_create_custom: code object too small (nbytes < 64)"; return MPOPIS_ERR_ARG; }
+    if (memcmp(code_object, kElf, 4) != 0 && memcmp(code_object, kBundle, sizeof kBundle - 1) != 0) {
+        g_create_error = "mpopis_create_custom: not a code object (neither an ELF nor a clang offload bundle: bad magic)"; return MPOPIS_ERR_ARG;
+    }
+    if (!code_object_complete((const unsigned char*)code_object, nbytes)) {
+        g_create_error = "mpopis_create_custom: the code object is truncated (its own tables reach past nbytes)"; return MPOPIS_ERR_ARG;
+    }
+    if (state_size < 1 || state_size > MPOPIS_ENV_MAX_STATE) { g_create_error = "mpopis_create_custom: state_size must be 1..64"; return MPOPIS_ERR_ARG; }
+    if (action_size < 1 || action_size > kMaxAs) { g_create_error = "mpopis_create_custom: action_size must be 1..16"; return MPOPIS_ERR_ARG; }
+    if (nparams < 0 || nparams > MPOPIS_ENV_MAX_PARAMS) { g_create_error = "mpopis_create_custom: nparams must be 0..64"; return MPOPIS_ERR_ARG; }
+    static_assert(MPOPIS_ENV_MAX_STATE == 64 && kMaxAs == 16 && MPOPIS_ENV_MAX_PARAMS == 64, "the messages above name the bounds");
+    mpopis_config cfg = *cfg_in;
+    cfg.env_kind = MPOPIS_ENV_CUSTOM; cfg.num_cars = 0;
+    if (const int rc = check_policy_config(&cfg, action_size)) return rc;
+    mpopis_handle* h = nullptr;
+    if (const int rc = create_handle(&cfg, action_size, state_size, &h)) return rc;
+    auto fail = [&](int code, const std::string& msg) { g_create_error = msg; mpopis_destroy(h); return code; };
+    // the module belongs to the handle (two handles with different code objects coexist); mpopis_destroy unloads it
+    hipError_t e = hipModuleLoadData(&h->custom.module, code_object);
+    if (e != hipSuccess) { h->custom.module = nullptr; return fail(MPOPIS_ERR_ARG, std::string("mpopis_create_custom: the code object does not load on this device (hipModuleLoadData: ") + hipGetErrorString(e) + "); build it for gfx950"); }
+    hipDeviceptr_t abi_ptr = nullptr; size_t abi_bytes = 0;
+    int32_t abi[4] = {0, 0, 0, 0};
+    if (hipModuleGetGlobal(&abi_ptr, &abi_bytes, h->custom.module, "mpopis_env_abi") != hipSuccess || abi_bytes != sizeof abi ||
+        hipMemcpyDtoH(abi, abi_ptr, sizeof abi) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MPOPIS_ERR_ARG, "mpopis_create_custom: the code object has no constant mpopis_env_abi (was it built with MPOPIS_DEFINE_ENV of mpopis_env.h?)");
+    }
+    if (abi[0] != MPOPIS_ENV_SDK_VERSION || abi[1] != state_size || abi[2] != action_size || abi[3] != nparams) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "mpopis_create_custom: the code object was built with SDK version %d for state_size %d, action_size %d, nparams %d; the call says version %d, %d, %d, %d",
+                 abi[0], abi[1], abi[2], abi[3], MPOPIS_ENV_SDK_VERSION, state_size, action_size, nparams);
+        return fail(MPOPIS_ERR_ARG, buf);
+    }
+    const struct { const char* name; hipFunction_t* fn; } kernels[] = {
+        {"mpopis_env_rollout", &h->custom.rollout}, {"mpopis_env_step", &h->custom.step}, {"mpopis_env_query", &h->custom.query}};
+    for (const auto& k : kernels)
+        if (hipModuleGetFunction(k.fn, h->custom.module, k.name) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MPOPIS_ERR_ARG, std::string("mpopis_create_custom: the code object has no kernel ") + k.name);
+        }
+    if (dalloc(h, &h->custom.d_params, (size_t)nparams)) return fail(MPOPIS_ERR_HIP, h->err);      // zeros until mpopis_set_env_params
+    h->custom.nparams = nparams;
+    h->custom_reset.assign((size_t)state_size, 0.0);
+    if (reset_state) memcpy(h->custom_reset.data(), reset_state, sizeof(double) * state_size);
+    if (mpopis_reset(h) != 0) return fail(MPOPIS_ERR_HIP, h->err);
+    *out = h;
+    return MPOPIS_OK;
+}
+
+// the part of a create call that runs on the device; as / ss: action and state size of the env
+static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle** out) {
+    const bool car = cfg->env_kind == MPOPIS_ENV_CAR;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available (the engine has no CPU fallback)"; return MPOPIS_ERR_HIP; }
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_error = "bad device ordinal"; return MPOPIS_ERR_ARG; }
@@ -222,8 +322,8 @@ int mpopis_create(const mpopis_config* cfg, mpopis_handle** out) {
     if (const char* e = getenv("MPOPIS_DEBUG_LAUNCH")) h->debug_launch = atoi(e) != 0;
     if (const char* e = getenv("MPOPIS_NSPLIT")) { h->nsplit = std::max(1, std::min((int)mpopis_handle::kMaxSplit, atoi(e))); h->split_auto = false; h->split_pinned = true; }   // experiments / profiling: pins the schedule, mpopis_set_overlap is then ignored
     h->B = cfg->batch; h->B_full = cfg->batch; h->K = cfg->num_samples; h->T = cfg->horizon;
-    h->as = car ? 2 * cfg->num_cars : 1;
-    h->ss = car ? 8 * cfg->num_cars : (cfg->env_kind == MPOPIS_ENV_CARTPOLE ? 4 : 2);
+    h->as = as;
+    h->ss = ss;
     h->cs = h->as * h->T;
     h->N = (cfg->policy == MPOPIS_POL_MPPI || cfg->policy == MPOPIS_POL_GMPPI) ? 1 : std::max(1, cfg->ais_its);
     h->gamma = cfg->lambda * (1 - cfg->alpha);
@@ -234,6 +334,7 @@ int mpopis_create(const mpopis_config* cfg, mpopis_handle** out) {
     default_cp_params(p); h->env.cp = make_cp_params(p);
     for (int i = 0; i < kMaxAs; ++i) { h->env.lo[i] = -1.0; h->env.hi[i] = 1.0; }
     h->env.track = Track{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr};
+    h->env.custom = cfg->env_kind == MPOPIS_ENV_CUSTOM ? &h->custom : nullptr;
     const int B = h->B, K = h->K, cs = h->cs;
     const size_t nn = (size_t)cs * cs;
     int rc = 0;
@@ -309,6 +410,7 @@ void mpopis_destroy(mpopis_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto st : h->xstream) if (st) (void)hipStreamSynchronize(st);
     for (void* p : h->allocs) (void)hipFree(p);
+    if (h->custom.module) (void)hipModuleUnload(h->custom.module);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
     if (h->h_call) (void)hipHostFree(h->h_call);
     if (h->h_coop_timeouts) (void)hipHostFree(h->h_coop_timeouts);
@@ -324,7 +426,12 @@ void mpopis_destroy(mpopis_handle* h) {
 
 int mpopis_set_env_params(mpopis_handle* h, const double* p, int32_t n) {
     if (!h || !p) return MPOPIS_ERR_ARG;
-    if (h->env.kind == MPOPIS_ENV_CAR) {
+    if (h->env.kind == MPOPIS_ENV_CUSTOM) {
+        if (n != h->custom.nparams) { h->err = "custom env expects " + std::to_string(h->custom.nparams) + " parameters"; return MPOPIS_ERR_ARG; }
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        HIPCHK(h, hipMemcpyAsync(h->custom.d_params, p, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, wait_stream(h->stream));
+    } else if (h->env.kind == MPOPIS_ENV_CAR) {
         if (n != MPOPIS_CAR_NPARAMS) { h->err = "car env expects 20 parameters"; return MPOPIS_ERR_ARG; }
         h->env.car = make_car_params(p);
     } else if (h->env.kind == MPOPIS_ENV_CARTPOLE) {
@@ -378,7 +485,9 @@ int mpopis_reset(mpopis_handle* h) {
     std::vector<double> x((size_t)h->B * h->ss, 0.0);
     for (int b = 0; b < h->B; ++b) {
         double* s = x.data() + (size_t)b * h->ss;
-        if (h->env.kind == MPOPIS_ENV_CAR) {
+        if (h->env.kind == MPOPIS_ENV_CUSTOM) {
+            if (!h->custom_reset.empty()) memcpy(s, h->custom_reset.data(), sizeof(double) * h->ss);      // reset_state of mpopis_create_custom
+        } else if (h->env.kind == MPOPIS_ENV_CAR) {
             for (int c = 0; c < h->env.ncars; ++c) {            // car_racing.jl:215-223; multi-car_racing.jl:160-180
                 const int ii = c + 1;
                 if (ii >= 2) s[8 * c] = (ii % 2 == 0) ? (ii / 2.0 * 5.0) : ((1 - ii) / 2.0 * 5.0);
@@ -546,7 +655,7 @@ int mpopis_env_step(mpopis_handle* h, const double* action, double* reward) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpyAsync(h->d_control, action, sizeof(double) * h->B * h->as, hipMemcpyHostToDevice, h->stream));
     fill_i32(h->d_status, 0, h->B, h->stream);
-    launch_env_step(h->env, h->d_x, h->d_t, h->d_done, h->d_control, h->d_reward, h->d_status, nullptr, h->B, h->stream);
+    HIPCHK(h, launch_env_step(h->env, h->d_x, h->d_t, h->d_done, h->d_control, h->d_reward, h->d_status, nullptr, h->B, h->stream));
     if (reward) HIPCHK(h, hipMemcpyAsync(reward, h->d_reward, sizeof(double) * h->B, hipMemcpyDeviceToHost, h->stream));
     return sync_status(h);
 }
@@ -557,7 +666,7 @@ int mpopis_env_query(mpopis_handle* h, double* reward, int32_t* within, double* 
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, NC = std::max(1, h->env.ncars);
     if (!h->d_qdist) { if (dalloc(h, &h->d_qdist, (size_t)B * NC) || dalloc(h, &h->d_qbeta, (size_t)B * NC) || dalloc(h, &h->d_qwithin, B)) return MPOPIS_ERR_HIP; }
-    launch_env_query(h->env, h->d_x, h->d_done, h->d_reward, h->d_qwithin, h->d_qdist, h->d_qbeta, B, h->stream);
+    HIPCHK(h, launch_env_query(h->env, h->d_x, h->d_t, h->d_done, h->d_reward, h->d_qwithin, h->d_qdist, h->d_qbeta, B, h->stream));
     if (reward) HIPCHK(h, hipMemcpyAsync(reward, h->d_reward, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
     if (within) HIPCHK(h, hipMemcpyAsync(within, h->d_qwithin, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
     if (dist) HIPCHK(h, hipMemcpyAsync(dist, h->d_qdist, sizeof(double) * B * NC, hipMemcpyDeviceToHost, h->stream));
@@ -794,7 +903,10 @@ void mpopis_handle::rollout(const double* Ucur, const double* Uorig, const doubl
     a.cmin = weights_in_moments ? d_cmin : nullptr; a.status = weights_in_moments ? d_status : nullptr;
     a.share = coop_share;
     time_begin(0);
-    if (!launch_rollout(a, stream) && launch_err.empty()) launch_err = "rollout: no kernel for this env (num_cars " + std::to_string(env.ncars) + ")";
+    hipError_t custom_err = hipSuccess;
+    if (!launch_rollout(a, stream, &custom_err) && launch_err.empty())
+        launch_err = env.kind == MPOPIS_ENV_CUSTOM ? std::string("rollout: launching the custom env's kernel failed: ") + hipGetErrorString(custom_err)
+                                                   : "rollout: no kernel for this env (num_cars " + std::to_string(env.ncars) + ")";
     time_end();
 }
 

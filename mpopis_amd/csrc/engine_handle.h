@@ -23,6 +23,8 @@ struct mpopis_handle {
     int nsplit = 1;                                                            // parts the batch is split into when split_auto is off
     bool split_auto = true;                                                    // default schedule (one stream); false: nsplit parts (mpopis_set_overlap)
     mpopis::EnvDesc env{};
+    mpopis::CustomEnv custom;              // MPOPIS_ENV_CUSTOM: the caller's code object (env.custom points here); unloaded in mpopis_destroy
+    std::vector<double> custom_reset;      // ... and the state mpopis_reset restores (ss doubles)
     std::string err;
     std::vector<void*> allocs;
     // resident env + policy state

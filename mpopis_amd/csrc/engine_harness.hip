@@ -124,7 +124,8 @@ int mpopis_handle::run_trials(int num_steps, int laps, double* records, double* 
         if (!chain_np) chains_fork();
         alive_gate = d_alive;
         int rc = chains_step(false, [&] {                       // (runs once per part, with B / stream / the slot pointers narrowed to that part)
-            launch_env_step(env, d_x, d_t, d_done, d_control, d_reward, d_status, d_alive, B, stream);
+            const hipError_t e = launch_env_step(env, d_x, d_t, d_done, d_control, d_reward, d_status, d_alive, B, stream);
+            if (e != hipSuccess && launch_err.empty()) launch_err = std::string("env step: launching the custom env's kernel failed: ") + hipGetErrorString(e);
             hipLaunchKernelGGL(k_harness_update, dim3((B + 63) / 64), dim3(64), 0, stream, env, d_x, d_done, d_reward, d_iters, d_hs, d_alive,
                                d_control, d_actlog, s, num_steps, laps, K, B,
                                StateNoise{noise_sx, noise_sy, noise_spsi, noisy ? d_seeds : (const uint64_t*)nullptr, d_rng_tab});

@@ -256,12 +256,29 @@ __global__ void __launch_bounds__(64) k_env_query(EnvDesc env, const double* x, 
     if (reward) reward[b] = rew;
     if (within) within[b] = win;
 }
-void launch_env_query(const EnvDesc& env, const double* x, const int* done, double* reward, int* within, double* dist, double* beta, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_env_query, dim3(B), dim3(64), 0, s, env, x, done, reward, within, dist, beta);
+// A caller's env (include/mpopis_env.h): the step / query kernel of its code object, one lane per slot.  The built-in kernels above treat
+// every kind that is not the car as one of the two simple envs, so a custom handle must never reach them.
+static hipError_t launch_custom_env_kernel(hipFunction_t fn, const EnvDesc& env, const double* x, const int* t, const int* done, const double* action,
+                                     double* reward, int* status, const int* alive, int* within, int B, hipStream_t s) {
+    mpopis_env_step_args k{};
+    k.x = (uint64_t)x; k.t = (uint64_t)t; k.done = (uint64_t)done; k.action = (uint64_t)action; k.reward = (uint64_t)reward;
+    k.status = (uint64_t)status; k.alive = (uint64_t)alive; k.within = (uint64_t)within; k.params = (uint64_t)env.custom->d_params;
+    k.B = B;
+    for (int i = 0; i < kMaxAs; ++i) { k.lo[i] = env.lo[i]; k.hi[i] = env.hi[i]; }
+    void* params[] = {&k};
+    return hipModuleLaunchKernel(fn, (B + 63) / 64, 1, 1, 64, 1, 1, 0, s, params, nullptr);
 }
 
-void launch_env_step(const EnvDesc& env, double* x, int* t, int* done, const double* action, double* reward, int* status, const int* alive, int B, hipStream_t s) {
+hipError_t launch_env_query(const EnvDesc& env, const double* x, const int* t, const int* done, double* reward, int* within, double* dist, double* beta, int B, hipStream_t s) {
+    if (env.kind == MPOPIS_ENV_CUSTOM) return launch_custom_env_kernel(env.custom->query, env, x, t, done, nullptr, reward, nullptr, nullptr, within, B, s);
+    hipLaunchKernelGGL(k_env_query, dim3(B), dim3(64), 0, s, env, x, done, reward, within, dist, beta);
+    return hipSuccess;
+}
+
+hipError_t launch_env_step(const EnvDesc& env, double* x, int* t, int* done, const double* action, double* reward, int* status, const int* alive, int B, hipStream_t s) {
+    if (env.kind == MPOPIS_ENV_CUSTOM) return launch_custom_env_kernel(env.custom->step, env, x, t, done, action, reward, status, alive, nullptr, B, s);
     hipLaunchKernelGGL(k_env_step, dim3(B), dim3(64), 0, s, env, x, t, done, action, reward, status, alive);
+    return hipSuccess;
 }
 
 }  // namespace mpopis

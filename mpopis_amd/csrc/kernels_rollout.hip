@@ -518,7 +518,25 @@ static bool launch_car_rollout(const RolloutArgs& a, bool tl, size_t lds, hipStr
     return true;
 }
 
-bool launch_rollout(const RolloutArgs& a, hipStream_t st) {
+// A caller's env (include/mpopis_env.h): the rollout kernel of its code object, same grid as k_rollout_simple.  The built-in kernels treat
+// every kind that is not the car as one of the two simple envs, so a custom handle must never reach them.
+static bool launch_custom_rollout(const RolloutArgs& a, hipStream_t st, hipError_t* err) {
+    const CustomEnv* ce = a.env.custom;
+    if (!ce || !ce->rollout) { if (err) *err = hipErrorInvalidHandle; return false; }
+    mpopis_env_rollout_args k{};
+    k.x0 = (uint64_t)a.x0; k.t0 = (uint64_t)a.t0; k.done0 = (uint64_t)a.done0; k.Ucur = (uint64_t)a.Ucur; k.Uorig = (uint64_t)a.Uorig;
+    k.E = (uint64_t)a.E; k.gvec = (uint64_t)a.gvec; k.cost = (uint64_t)a.cost; k.traj = (uint64_t)a.traj; k.active = (uint64_t)a.active;
+    k.iters = (uint64_t)a.iters; k.params = (uint64_t)ce->d_params;
+    k.B = a.B; k.K = a.K; k.T = a.T; k.cs = a.cs; k.iter_n = a.iter_n;
+    for (int i = 0; i < kMaxAs; ++i) { k.lo[i] = a.env.lo[i]; k.hi[i] = a.env.hi[i]; }
+    void* params[] = {&k};
+    const hipError_t e = hipModuleLaunchKernel(ce->rollout, (a.K + 63) / 64, a.B, 1, 64, 1, 1, 0, st, params, nullptr);
+    if (err) *err = e;
+    return e == hipSuccess;
+}
+
+bool launch_rollout(const RolloutArgs& a, hipStream_t st, hipError_t* custom_err) {
+    if (a.env.kind == MPOPIS_ENV_CUSTOM) return launch_custom_rollout(a, st, custom_err);
     if (a.env.kind == MPOPIS_ENV_MOUNTAINCAR || a.env.kind == MPOPIS_ENV_CARTPOLE) {
         const auto kernel = a.env.kind == MPOPIS_ENV_CARTPOLE ? k_rollout_simple<4> : k_rollout_simple<2>;     // state size 4 / 2
         hipLaunchKernelGGL(kernel, dim3((a.K + 63) / 64, a.B), dim3(64), 0, st, a);

@@ -6,6 +6,7 @@ reward are the device kernels (mpopis_env_step / mpopis_env_query); nothing is e
   MultiCarRacingEnv   src/envs/multi-car_racing.jl:2-64
   MountainCarEnv      RL.jl MountainCarEnv(continuous=true) + src/examples/mountaincar_example.jl:4-22
   CartPoleEnv         RL.jl CartPoleEnv(continuous=true) + src/examples/cartpole_example.jl:3-6
+  CustomEnv           any AbstractEnv of the caller: env(a) / reward(env) as device functions (include/mpopis_env.h)
   Track               src/envs/car_racing_tracks/car_racing_tracks.jl:2-34
 """
 import math
@@ -76,7 +77,7 @@ class _EnvBase:
     def _mk_engine(self, device=0):
         self._eng = Engine(self.kind, self.ncars, "gmppi", num_samples=1, horizon=1, batch=1, lam=1.0,
                            device=device, track=self.track.arrays() if self.kind == "car" else None,
-                           env_params=self._param_vector())
+                           env_params=self._param_vector(), custom_env=self if self.kind == "custom" else None)
         self._push()
 
     def _push(self):
@@ -259,6 +260,48 @@ class CartPoleEnv(_EnvBase):
             self._push()
 
 
+def pointmass_source():
+    """Path of the example env source the package ships (env_examples/pointmass.hip: a planar point mass, SS = 5, AS = 3, NP = 9)."""
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "env_examples", "pointmass.hip")
+
+
+class CustomEnv(_EnvBase):
+    """An env of your own under every policy: env(a) and reward(env) are two device functions written against include/mpopis_env.h.
+    `code_object_or_source`: the path of a built code object (.hsaco / .co), its bytes, or the path of the source, which is then
+    compiled with mpopis_amd.build.build_env (hipcc --genco for gfx950).  `params`: the parameter vector the two functions read;
+    `lo` / `hi`: action_space(env) per action (default [-1, 1]); `reset_state`: what reset!(env) restores (default zeros)."""
+
+    def __init__(self, code_object_or_source, state_size, action_size, params=(), lo=None, hi=None, reset_state=None, device=0):
+        co = code_object_or_source
+        if not isinstance(co, (bytes, bytearray)):
+            co = os.fspath(co)
+            if not co.endswith((".hsaco", ".co")):
+                from .build import build_env
+                co = build_env(co)
+        self.code_object = co
+        self.state_size, self.action_size = int(state_size), int(action_size)
+        self.params = _f64(params).reshape(-1)
+        self.lo = None if lo is None else _f64(lo).reshape(-1)
+        self.hi = None if hi is None else _f64(hi).reshape(-1)
+        self.reset_state = np.zeros(self.state_size) if reset_state is None else _f64(reset_state).reshape(-1).copy()
+        if self.reset_state.size != self.state_size:
+            raise MPOPISError(ERR_ARG, "reset_state must hold state_size values")
+        self.kind, self.ncars, self.as_, self.ss = "custom", 0, self.action_size, self.state_size
+        self.track, self.rng = None, None
+        self._eng_device = device
+        self.reset(_make=False)
+        self._mk_engine(device)
+
+    def _param_vector(self):
+        return self.params
+
+    def reset(self, state=None, _make=True):
+        self.state = self.reset_state.copy() if state is None else _f64(state).copy()
+        self.t, self.done = 0, False
+        if _make:
+            self._push()
+
+
 # ---- RLBase-style free functions used by the reference's callers ------------------------------------
 def state(env):
     return env.state
@@ -270,7 +313,8 @@ def is_terminated(env):
 
 def action_space(env):
     """(leftendpoint, rightendpoint): car_racing.jl:156-159; multi-car_racing.jl:75-84; RL.jl -1.0..1.0"""
-    return -np.ones(env.as_), np.ones(env.as_)
+    lo, hi = getattr(env, "lo", None), getattr(env, "hi", None)                  # CustomEnv: the bounds it was given
+    return (-np.ones(env.as_) if lo is None else lo.copy()), (np.ones(env.as_) if hi is None else hi.copy())
 
 
 def reward(env):

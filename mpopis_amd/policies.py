@@ -51,7 +51,7 @@ class AbstractPathIntegralPolicy:
         self._eng = Engine(env.kind, env.ncars, self._kind, num_samples=num_samples, horizon=horizon, batch=1, lam=λ,
                            alpha=α, seed=seed, device=device, log_trajectories=log,
                            track=env.track.arrays() if env.kind == "car" else None, env_params=env._param_vector(),
-                           cov=cov, U0=U0, **extra)
+                           cov=cov, U0=U0, custom_env=env if env.kind == "custom" else None, **extra)
         p = _Params()
         p.num_samples, p.horizon, p.λ, p.α, p.U0 = num_samples, horizon, λ, α, U0
         p.ss, p.as_, p.cs, p.log = env.ss, as_, as_ * horizon, log
