@@ -54,7 +54,12 @@ extern "C" {
  *    Later gained the env kind MPOPIS_ENV_CUSTOM = 3 and ONE entry point, mpopis_create_custom (a handle on a caller-supplied env compiled to a
  *    gfx950 code object, include/mpopis_env.h); mpopis_config and every other entry point are unchanged.  A library that predates it does not
  *    export the symbol, which is how a caller detects support (env_kind = 3 was "unknown env kind" to mpopis_create before and is still refused
- *    there, now with a message that names the new entry point). */
+ *    there, now with a message that names the new entry point).
+ *    Later gained ONE more entry point, mpopis_set_env_table: a read-only table of doubles (a path, an obstacle list, a cost grid, a lookup
+ *    curve), per handle or per trial slot, for custom envs built with MPOPIS_DEFINE_ENV_TABLE of include/mpopis_env.h, whose two functions take
+ *    (..., const double *tab, int ntab).  MPOPIS_DEFINE_ENV, its kernels, mpopis_config and every other entry point are unchanged; a library
+ *    that predates it does not export the symbol, which is how a caller detects support (its mpopis_create_custom refuses such a code object:
+ *    it finds none of the kernels it looks for). */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -142,6 +147,7 @@ int  mpopis_create(const mpopis_config *cfg, mpopis_handle **out);
  *   state_size 1..64, action_size 1..16, nparams 0..64: must equal what the code object was built with (cs = action_size H obeys the
  *                  per-policy limits listed at mpopis_config.num_cars)
  *   reset_state    state_size doubles that mpopis_reset restores in every slot (with t = 0, done = 0), or NULL for zeros
+ * A code object built with MPOPIS_DEFINE_ENV_TABLE also takes a data table: mpopis_set_env_table below.
  * On such a handle mpopis_set_env_params takes exactly nparams doubles (default: zeros), mpopis_set_action_bounds holds per action
  * (default [-1, 1]), mpopis_env_query returns reward(env) and within = 1, mpopis_run_trials ends a slot when the env sets done, and
  * mpopis_set_track / mpopis_set_state_noise have no effect; everything else works as on a built-in env.  The module is unloaded by
@@ -153,6 +159,17 @@ void mpopis_destroy(mpopis_handle *h);
 
 /* ---- env description (the env protocol the path consumes) ------------------------ */
 int  mpopis_set_env_params(mpopis_handle *h, const double *p, int32_t n);   /* env.params, env.dt, env.δt */
+/* The data table of a custom env built with MPOPIS_DEFINE_ENV_TABLE (include/mpopis_env.h): what the reference keeps in the fields of its env
+ * struct beside the state -- env.track of CarRacingEnv (src/envs/car_racing.jl:28-40) is one -- handed to the env's step and reward functions as
+ * (tab, ntab) and indexable at run time.
+ *   n         doubles per slot, 0..MPOPIS_ENV_MAX_TABLE (2^20); n = 0 clears the table (data may then be NULL): the env runs with ntab == 0,
+ *             as it does before the first call
+ *   per_slot  0: data holds n doubles that every slot sees; otherwise B*n doubles, slot b sees data[b*n .. b*n+n)
+ * May be called any number of times, with a different n each time; the call waits for everything the handle has queued before the table is
+ * replaced.  Values are the caller's business (non-finite ones are not refused).  Tables of up to MPOPIS_ENV_TABLE_LDS_DOUBLES (4096) doubles are
+ * staged in LDS by the rollout kernel, larger ones are read from global memory; results do not depend on which.
+ * MPOPIS_ERR_ARG: a handle that is not custom, a code object without a table, n out of range, NULL data with n > 0. */
+int  mpopis_set_env_table(mpopis_handle *h, const double *data, int64_t n, int32_t per_slot);
 int  mpopis_set_track(mpopis_handle *h, const double *x, const double *y, const double *w, int32_t P);
                                                                   /* env.track.{x′,y′,lane_width′} car_racing_tracks.jl:21-23 */
 int  mpopis_set_action_bounds(mpopis_handle *h, const double *lo, const double *hi); /* action_space(env) */

@@ -28,6 +28,21 @@
  * A host compiler sees MPOPIS_ENV_FN as `static inline` and MPOPIS_DEFINE_ENV as two plain C functions (mpopis_env_host_step,
  * mpopis_env_host_reward) plus the constant, so the same source builds into a CPU shim for testing the dynamics without a GPU
  * (g++ -x c++ -shared -fPIC -I include my_env.hip).
+ *
+ * An env with a data table -- a reference path, an obstacle list, a cost grid, a lookup curve: data sized at run time -- takes two more
+ * arguments and the second macro:
+ *
+ *     MPOPIS_ENV_FN void   my_step  (double* s, int* t, int* done, const double* a, const double* p, const double* tab, int ntab) { ... }
+ *     MPOPIS_ENV_FN double my_reward(const double* s, int t, int done, const double* p, const double* tab, int ntab) { ... }
+ *     MPOPIS_DEFINE_ENV_TABLE(SS, AS, NP, my_step, my_reward)
+ *
+ *   tab   the ntab doubles the handle holds for this trial slot (mpopis_set_env_table: one table for all slots, or one per slot), read-only.
+ *         Index it at run time, wave-uniformly (a loop over waypoints) or per lane (the grid cell under a position); ntab == 0 until a table
+ *         is set, and tab must not be dereferenced then.  The rules for s, a and p stay as above.
+ *
+ * A table of up to MPOPIS_ENV_TABLE_LDS_DOUBLES doubles is staged in LDS once per workgroup of four waves (mpopis_env_rollout_tab); a larger one,
+ * up to MPOPIS_ENV_MAX_TABLE, is read from global memory through the constant address space (mpopis_env_rollout_gtab).  The engine picks the
+ * kernel by the size of the table that is set; the two functions are the same source in both, and in the host build.
  */
 #ifndef MPOPIS_ENV_H
 #define MPOPIS_ENV_H
@@ -39,6 +54,10 @@
 #define MPOPIS_ENV_MAX_ACTION 16     /* AS in 1..16 */
 #define MPOPIS_ENV_MAX_PARAMS 64     /* NP in 0..64 */
 #define MPOPIS_ENV_ERR_ACTION (-3)   /* == MPOPIS_ERR_ACTION of mpopis.h */
+#define MPOPIS_ENV_TABLE_VERSION 1
+#define MPOPIS_ENV_TABLE_LDS_DOUBLES 4096      /* largest table staged in LDS: 32 KiB, up to five workgroups per CU */
+#define MPOPIS_ENV_MAX_TABLE (1 << 20)         /* ntab in 0..2^20 doubles per slot */
+#define MPOPIS_ENV_TABLE_THREADS 256           /* workgroup of the two table rollout kernels: four waves */
 
 /* Kernel arguments: plain data with fixed-width fields, shared by the generated kernels and the engine that launches them (both include
  * this header).  Every uint64_t is a device address (0 = absent). */
@@ -72,6 +91,21 @@ typedef struct {
     double lo[MPOPIS_ENV_MAX_ACTION], hi[MPOPIS_ENV_MAX_ACTION];
 } mpopis_env_step_args;
 
+/* Arguments of the table kernels (MPOPIS_DEFINE_ENV_TABLE): the fields above, then the table. */
+typedef struct {
+    mpopis_env_rollout_args r;
+    uint64_t table;         /* const double [ntab], or [B][table_stride] when every slot has its own; 0 when ntab == 0 */
+    int64_t table_stride;   /* doubles from one slot's table to the next; 0: one table shared by all slots              */
+    int32_t ntab, pad;
+} mpopis_env_rollout_tab_args;
+
+typedef struct {
+    mpopis_env_step_args s;
+    uint64_t table;
+    int64_t table_stride;
+    int32_t ntab, pad;
+} mpopis_env_step_tab_args;
+
 #define MPOPIS_ENV_CHECK_SIZES_(SS, AS, NP)                                                                            \
     static_assert((SS) >= 1 && (SS) <= MPOPIS_ENV_MAX_STATE, "MPOPIS_DEFINE_ENV: state size must be 1..64");           \
     static_assert((AS) >= 1 && (AS) <= MPOPIS_ENV_MAX_ACTION, "MPOPIS_DEFINE_ENV: action size must be 1..16");         \
@@ -98,6 +132,13 @@ __device__ __forceinline__ global_i32 as_global_i32(uint64_t a) { return (global
 /* the user's two functions travel as template arguments: MPOPIS_DEFINE_ENV names them at file scope, where no name of this header can hide them */
 typedef void (*step_fn)(double* s, int* t, int* done, const double* a, const double* p);
 typedef double (*reward_fn)(const double* s, int t, int done, const double* p);
+typedef void (*step_tab_fn)(double* s, int* t, int* done, const double* a, const double* p, const double* tab, int ntab);
+typedef double (*reward_tab_fn)(const double* s, int t, int done, const double* p, const double* tab, int ntab);
+
+/* One body per kernel serves both kinds of env: it is instantiated on the two functions themselves and calls them by their type. */
+template <class F> struct takes_table { static constexpr bool value = false; };
+template <> struct takes_table<step_tab_fn> { static constexpr bool value = true; };
+template <> struct takes_table<reward_tab_fn> { static constexpr bool value = true; };
 
 /* get_model_controls' clamp (src/utils.jl:55-67); NaN passes through */
 __device__ __forceinline__ double clamp(double v, double lo, double hi) { return v > hi ? hi : (v < lo ? lo : v); }
@@ -112,15 +153,15 @@ __device__ __forceinline__ void raise_action(global_i32 p) {
     }
 }
 
-/* simulate_model + rollout_model for one slot's K samples: lane = one rollout, one wave per workgroup, grid (ceil(K / 64), B).
+/* simulate_model + rollout_model for one slot's K samples: lane = one rollout, workgroups of WG threads (MPOPIS_DEFINE_ENV: one wave), grid (ceil(K / WG), B).
  *   V = pol.U + E[:, k]; control cost of the unclamped V; a = clamp(V); env(a); cost -= reward(env); logger     (:261-278, utils.jl:129-144)
  * State and action are registers (every loop over SS / AS is unrolled); E is read coalesced over k; everything else is wave-uniform. */
-template <int SS, int AS, int NP, step_fn STEP, reward_fn REWARD>
-__device__ __forceinline__ void rollout(const mpopis_env_rollout_args& a) {
+template <int SS, int AS, int NP, auto STEP, auto REWARD, int WG = 64, bool GATE = true>
+__device__ __forceinline__ void rollout(const mpopis_env_rollout_args& a, const double* tab = nullptr, int ntab = 0) {
     const int b = blockIdx.y;
-    if (a.active && !as_uniform_i32(a.active)[b]) return;                     /* AIS early break */
+    if (GATE && a.active && !as_uniform_i32(a.active)[b]) return;             /* AIS early break (GATE = false: the caller has looked) */
     const int K = a.K, T = a.T;
-    const int k = blockIdx.x * 64 + threadIdx.x;
+    const int k = blockIdx.x * WG + threadIdx.x;
     const bool valid = k < K;
     const int kk = valid ? k : K - 1;                                          /* idle lanes duplicate the last sample and do not store */
     const size_t cs = (size_t)AS * T;
@@ -152,8 +193,13 @@ __device__ __forceinline__ void rollout(const mpopis_env_rollout_args& a) {
         /* a NaN action: RL.jl's act! asserts `a in action_space(env)` and the rollout dies there.  A reward need not look at the state's
          * values, so the cost is poisoned here: a non-finite cost is what raises MPOPIS_ERR_ACTION when the weights are formed */
         if (nan_action) cost = NAN;
-        STEP(s, &t_env, &done, act, p);
-        cost -= REWARD(s, t_env, done, p);                                /* utils.jl:138 */
+        if constexpr (takes_table<decltype(STEP)>::value) {
+            STEP(s, &t_env, &done, act, p, tab, ntab);
+            cost -= REWARD(s, t_env, done, p, tab, ntab);
+        } else {
+            STEP(s, &t_env, &done, act, p);
+            cost -= REWARD(s, t_env, done, p);                                /* utils.jl:138 */
+        }
         if (log) {                                                             /* trajectories[k][t, :] utils.jl:140 */
 #pragma unroll
             for (int i = 0; i < SS; ++i) tr[(size_t)i * T + t] = s[i];
@@ -164,9 +210,42 @@ __device__ __forceinline__ void rollout(const mpopis_env_rollout_args& a) {
     if (a.iters && blockIdx.x == 0 && threadIdx.x == 0) as_global_i32(a.iters)[b] = a.iter_n;
 }
 
+/* MPOPIS_DEFINE_ENV_TABLE: four waves per workgroup.  LDS form: the workgroup copies the slot's table into dynamic LDS (ntab * 8 bytes, sized at
+ * launch: a small table costs no occupancy), coalesced and with eight loads in flight per thread; after the one barrier, waves without a sample
+ * leave.  Global form: the table is wave-uniform and not written while the kernel runs (mpopis_set_env_table waits for the handle's streams),
+ * so it is read like the parameters: uniform indices by scalar loads, per-lane indices by vector loads. */
+template <int SS, int AS, int NP, bool LDS, step_tab_fn STEP, reward_tab_fn REWARD>
+__device__ __forceinline__ void rollout_tab(const mpopis_env_rollout_tab_args& a) {
+    constexpr int WG = MPOPIS_ENV_TABLE_THREADS;
+    const int b = blockIdx.y;
+    if (a.r.active && !as_uniform_i32(a.r.active)[b]) return;                 /* the whole workgroup, ahead of the barrier */
+    const int ntab = a.ntab;
+    if constexpr (LDS) {
+        extern __shared__ double mpopis_env_tab_lds[];
+        const global_f64 src = as_global_f64(a.table) + (size_t)b * a.table_stride;
+        const int tid = threadIdx.x;
+        for (int e0 = tid; e0 < ntab; e0 += WG * 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = src[min(e0 + u * WG, ntab - 1)];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) if (e0 + u * WG < ntab) mpopis_env_tab_lds[e0 + u * WG] = v[u];
+        }
+        __syncthreads();
+        if ((int)(threadIdx.x & ~63u) >= a.r.K - WG * (int)blockIdx.x) return;         /* a wave with no sample at all */
+        rollout<SS, AS, NP, STEP, REWARD, WG, false>(a.r, mpopis_env_tab_lds, ntab);
+    } else {
+        if ((int)(threadIdx.x & ~63u) >= a.r.K - WG * (int)blockIdx.x) return;
+        rollout<SS, AS, NP, STEP, REWARD, WG, false>(a.r, (const double*)(as_uniform_f64(a.table) + (size_t)b * a.table_stride), ntab);
+    }
+}
+
+/* the cold kernels read a slot's table from global memory (one lane per slot: nothing to stage for) */
+__device__ __forceinline__ const double* slot_table(uint64_t table, int64_t stride, int b) { return (const double*)(as_global_f64(table) + (size_t)b * stride); }
+
 /* env(action); reward(env) for the B resident envs, one lane per slot */
-template <int SS, int AS, int NP, step_fn STEP, reward_fn REWARD>
-__device__ __forceinline__ void env_step(const mpopis_env_step_args& a) {
+template <int SS, int AS, int NP, auto STEP, auto REWARD>
+__device__ __forceinline__ void env_step(const mpopis_env_step_args& a, uint64_t table = 0, int64_t table_stride = 0, int ntab = 0) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.B) return;
     if (a.alive && !as_global_i32(a.alive)[b]) return;
@@ -182,16 +261,19 @@ __device__ __forceinline__ void env_step(const mpopis_env_step_args& a) {
 #pragma unroll
     for (int i = 0; i < SS; ++i) s[i] = xb[i];
     int t = as_global_i32(a.t)[b], done = as_global_i32(a.done)[b];
-    STEP(s, &t, &done, act, p);
+    if constexpr (takes_table<decltype(STEP)>::value) STEP(s, &t, &done, act, p, slot_table(table, table_stride, b), ntab);
+    else STEP(s, &t, &done, act, p);
 #pragma unroll
     for (int i = 0; i < SS; ++i) xb[i] = s[i];
     as_global_i32(a.t)[b] = t; as_global_i32(a.done)[b] = done;
-    if (a.reward) as_global_f64(a.reward)[b] = REWARD(s, t, done, p);
+    if (a.reward) {
+        if constexpr (takes_table<decltype(REWARD)>::value) as_global_f64(a.reward)[b] = REWARD(s, t, done, p, slot_table(table, table_stride, b), ntab);
+        else as_global_f64(a.reward)[b] = REWARD(s, t, done, p);
+    }
 }
-
 /* reward(env) of the resident state without stepping */
-template <int SS, int AS, int NP, step_fn STEP, reward_fn REWARD>
-__device__ __forceinline__ void env_query(const mpopis_env_step_args& a) {
+template <int SS, int AS, int NP, auto STEP, auto REWARD>
+__device__ __forceinline__ void env_query(const mpopis_env_step_args& a, uint64_t table = 0, int64_t table_stride = 0, int ntab = 0) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.B) return;
     const double* p = (const double*)as_uniform_f64(a.params);
@@ -199,7 +281,11 @@ __device__ __forceinline__ void env_query(const mpopis_env_step_args& a) {
     double s[SS];
 #pragma unroll
     for (int i = 0; i < SS; ++i) s[i] = xb[i];
-    if (a.reward) as_global_f64(a.reward)[b] = REWARD(s, as_global_i32(a.t)[b], as_global_i32(a.done)[b], p);
+    if (a.reward) {
+        const int t = as_global_i32(a.t)[b], done = as_global_i32(a.done)[b];
+        if constexpr (takes_table<decltype(REWARD)>::value) as_global_f64(a.reward)[b] = REWARD(s, t, done, p, slot_table(table, table_stride, b), ntab);
+        else as_global_f64(a.reward)[b] = REWARD(s, t, done, p);
+    }
     if (a.within) as_global_i32(a.within)[b] = 1;
 }
 
@@ -219,6 +305,25 @@ __device__ __forceinline__ void env_query(const mpopis_env_step_args& a) {
         mpopis_env::env_query<(SS), (AS), (NP), STEP, REWARD>(a);                                                                            \
     }
 
+/* An env with a table: the same constant, a second one {table version, largest table the LDS kernel stages} -- its presence tells the engine that
+ * the env takes a table -- and four kernels under names of their own. */
+#define MPOPIS_DEFINE_ENV_TABLE(SS, AS, NP, STEP, REWARD)                                                                                    \
+    MPOPIS_ENV_CHECK_SIZES_(SS, AS, NP)                                                                                                      \
+    extern "C" __device__ __attribute__((used)) const int32_t mpopis_env_abi[4] = {MPOPIS_ENV_SDK_VERSION, (SS), (AS), (NP)};                \
+    extern "C" __device__ __attribute__((used)) const int32_t mpopis_env_table_abi[2] = {MPOPIS_ENV_TABLE_VERSION, MPOPIS_ENV_TABLE_LDS_DOUBLES};  \
+    extern "C" __global__ void __launch_bounds__(MPOPIS_ENV_TABLE_THREADS) mpopis_env_rollout_tab(mpopis_env_rollout_tab_args a) {           \
+        mpopis_env::rollout_tab<(SS), (AS), (NP), true, STEP, REWARD>(a);                                                                    \
+    }                                                                                                                                        \
+    extern "C" __global__ void __launch_bounds__(MPOPIS_ENV_TABLE_THREADS) mpopis_env_rollout_gtab(mpopis_env_rollout_tab_args a) {          \
+        mpopis_env::rollout_tab<(SS), (AS), (NP), false, STEP, REWARD>(a);                                                                   \
+    }                                                                                                                                        \
+    extern "C" __global__ void __launch_bounds__(64) mpopis_env_step_tab(mpopis_env_step_tab_args a) {                                       \
+        mpopis_env::env_step<(SS), (AS), (NP), STEP, REWARD>(a.s, a.table, a.table_stride, a.ntab);                                            \
+    }                                                                                                                                        \
+    extern "C" __global__ void __launch_bounds__(64) mpopis_env_query_tab(mpopis_env_step_tab_args a) {                                      \
+        mpopis_env::env_query<(SS), (AS), (NP), STEP, REWARD>(a.s, a.table, a.table_stride, a.ntab);                                            \
+    }
+
 #else  /* host compiler: the env as two C functions */
 #define MPOPIS_ENV_FN static inline
 #define MPOPIS_DEFINE_ENV(SS, AS, NP, STEP, REWARD)                                                                                          \
@@ -226,6 +331,16 @@ __device__ __forceinline__ void env_query(const mpopis_env_step_args& a) {
     extern "C" const int32_t mpopis_env_abi[4] = {MPOPIS_ENV_SDK_VERSION, (SS), (AS), (NP)};                                                 \
     extern "C" void mpopis_env_host_step(double* s, int* t, int* done, const double* a, const double* p) { STEP(s, t, done, a, p); }         \
     extern "C" double mpopis_env_host_reward(const double* s, int t, int done, const double* p) { return REWARD(s, t, done, p); }
+#define MPOPIS_DEFINE_ENV_TABLE(SS, AS, NP, STEP, REWARD)                                                                                    \
+    MPOPIS_ENV_CHECK_SIZES_(SS, AS, NP)                                                                                                      \
+    extern "C" const int32_t mpopis_env_abi[4] = {MPOPIS_ENV_SDK_VERSION, (SS), (AS), (NP)};                                                 \
+    extern "C" const int32_t mpopis_env_table_abi[2] = {MPOPIS_ENV_TABLE_VERSION, MPOPIS_ENV_TABLE_LDS_DOUBLES};                             \
+    extern "C" void mpopis_env_host_step(double* s, int* t, int* done, const double* a, const double* p, const double* tab, int ntab) {      \
+        STEP(s, t, done, a, p, tab, ntab);                                                                                                   \
+    }                                                                                                                                        \
+    extern "C" double mpopis_env_host_reward(const double* s, int t, int done, const double* p, const double* tab, int ntab) {               \
+        return REWARD(s, t, done, p, tab, ntab);                                                                                             \
+    }
 #endif
 
 #endif  /* MPOPIS_ENV_H */

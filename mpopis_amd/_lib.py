@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "mpopis_seed", "mpopis_seed_slots", "mpopis_get_Sigma", "mpopis_rollout_costs", "mpopis_policy_step", "mpopis_env_step",
     "mpopis_env_query", "mpopis_get_trajectories", "mpopis_set_state_noise", "mpopis_run_trials", "mpopis_timing_enable", "mpopis_timing_read",
     "mpopis_timing_reset", "mpopis_bench_policy_steps",
-    "mpopis_create_custom", "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
+    "mpopis_create_custom", "mpopis_set_env_table", "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
 ]
 
 
@@ -71,6 +71,8 @@ def lib():
         L.mpopis_create.argtypes = [C.POINTER(Config), C.POINTER(H)]
         if hasattr(L, "mpopis_create_custom"):                  # (a MPOPIS_HIP_LIB build that predates custom envs still serves the built-in ones)
             L.mpopis_create_custom.argtypes = [C.POINTER(Config), C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(H)]
+        if hasattr(L, "mpopis_set_env_table"):
+            L.mpopis_set_env_table.argtypes = [H, _dp, C.c_int64, C.c_int32]
         L.mpopis_destroy.argtypes = [H]
         L.mpopis_destroy.restype = None
         L.mpopis_set_env_params.argtypes = [H, _dp, C.c_int32]

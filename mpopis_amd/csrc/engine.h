@@ -48,12 +48,23 @@ static_assert(kMaxAs == MPOPIS_ENV_MAX_ACTION && MPOPIS_ENV_ERR_ACTION == MPOPIS
 
 // A caller-supplied env (MPOPIS_ENV_CUSTOM, include/mpopis_env.h): the loaded code object, its three kernels and the device parameter
 // buffer.  Owned by the handle; the launchers below reach it through EnvDesc::custom (a HOST pointer: kernels never look at it).
+// An env built with MPOPIS_DEFINE_ENV_TABLE (has_table) has four kernels instead -- rollout is then the LDS form, rollout_gtab the global one --
+// and the table mpopis_set_env_table uploaded: ntab doubles per slot, shared (table_stride 0) or one per slot (table_stride == ntab).
 struct CustomEnv {
     hipModule_t module = nullptr;
-    hipFunction_t rollout = nullptr, step = nullptr, query = nullptr;
+    hipFunction_t rollout = nullptr, step = nullptr, query = nullptr, rollout_gtab = nullptr;
     double* d_params = nullptr;
     int nparams = 0;
+    bool has_table = false;
+    int table_lds_doubles = 0;        // largest table the code object's LDS kernel stages (mpopis_env_table_abi[1])
+    double* d_table = nullptr;        // the buffer (not in mpopis_handle::allocs: it grows); table_cap doubles
+    size_t table_cap = 0;
+    const double* table_view = nullptr;   // the table of the handle's first slot: d_table, moved with the slot views (shift_slots); null while ntab == 0
+    int64_t table_stride = 0;
+    int ntab = 0;
 };
+
+constexpr int kEnvTableLdsMaxDoubles = 8192;      // 64 KiB of dynamic LDS: what a kernel may be launched with without its limit being raised
 
 struct EnvDesc {
     int kind;        // MPOPIS_ENV_*

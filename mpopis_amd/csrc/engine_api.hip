@@ -274,8 +274,30 @@ int mpopis_create_custom(const mpopis_config* cfg_in, const void* code_object, u
                  abi[0], abi[1], abi[2], abi[3], MPOPIS_ENV_SDK_VERSION, state_size, action_size, nparams);
         return fail(MPOPIS_ERR_ARG, buf);
     }
-    const struct { const char* name; hipFunction_t* fn; } kernels[] = {
-        {"mpopis_env_rollout", &h->custom.rollout}, {"mpopis_env_step", &h->custom.step}, {"mpopis_env_query", &h->custom.query}};
+    // an env with a table (MPOPIS_DEFINE_ENV_TABLE) says so with a second constant and has four kernels under names of their own
+    hipDeviceptr_t tab_ptr = nullptr; size_t tab_bytes = 0;
+    int32_t tab_abi[2] = {0, 0};
+    if (hipModuleGetGlobal(&tab_ptr, &tab_bytes, h->custom.module, "mpopis_env_table_abi") == hipSuccess) {
+        if (tab_bytes != sizeof tab_abi || hipMemcpyDtoH(tab_abi, tab_ptr, sizeof tab_abi) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MPOPIS_ERR_ARG, "mpopis_create_custom: the code object's constant mpopis_env_table_abi cannot be read (two int32 expected)");
+        }
+        if (tab_abi[0] != MPOPIS_ENV_TABLE_VERSION || tab_abi[1] < 0 || tab_abi[1] > kEnvTableLdsMaxDoubles) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "mpopis_create_custom: the code object was built with env table version %d (LDS table limit %d doubles); this library knows version %d and stages at most %d",
+                     tab_abi[0], tab_abi[1], MPOPIS_ENV_TABLE_VERSION, kEnvTableLdsMaxDoubles);
+            return fail(MPOPIS_ERR_ARG, buf);
+        }
+        h->custom.has_table = true;
+        h->custom.table_lds_doubles = tab_abi[1];
+    } else {
+        (void)hipGetLastError();
+    }
+    struct kernel_name { const char* name; hipFunction_t* fn; };
+    const std::vector<kernel_name> kernels = h->custom.has_table
+        ? std::vector<kernel_name>{{"mpopis_env_rollout_tab", &h->custom.rollout}, {"mpopis_env_rollout_gtab", &h->custom.rollout_gtab},
+                                   {"mpopis_env_step_tab", &h->custom.step}, {"mpopis_env_query_tab", &h->custom.query}}
+        : std::vector<kernel_name>{{"mpopis_env_rollout", &h->custom.rollout}, {"mpopis_env_step", &h->custom.step}, {"mpopis_env_query", &h->custom.query}};
     for (const auto& k : kernels)
         if (hipModuleGetFunction(k.fn, h->custom.module, k.name) != hipSuccess) {
             (void)hipGetLastError();
@@ -410,6 +432,7 @@ void mpopis_destroy(mpopis_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto st : h->xstream) if (st) (void)hipStreamSynchronize(st);
     for (void* p : h->allocs) (void)hipFree(p);
+    if (h->custom.d_table) (void)hipFree(h->custom.d_table);
     if (h->custom.module) (void)hipModuleUnload(h->custom.module);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
     if (h->h_call) (void)hipHostFree(h->h_call);
@@ -441,6 +464,33 @@ int mpopis_set_env_params(mpopis_handle* h, const double* p, int32_t n) {
         if (n != MPOPIS_MOUNTAINCAR_NPARAMS) { h->err = "MountainCar expects 8 parameters"; return MPOPIS_ERR_ARG; }
         h->env.mc = make_mc_params(p);
     }
+    return MPOPIS_OK;
+}
+
+// The table of a caller's env (MPOPIS_DEFINE_ENV_TABLE).  A setup call: it waits for everything the handle has queued, on the part-chain streams
+// too, before the buffer is written or replaced -- the global-memory rollout kernel reads the table through the constant address space, which
+// holds only while nothing writes it under a running kernel.
+int mpopis_set_env_table(mpopis_handle* h, const double* data, int64_t n, int32_t per_slot) {
+    if (!h) return MPOPIS_ERR_ARG;
+    if (h->env.kind != MPOPIS_ENV_CUSTOM) { h->err = "mpopis_set_env_table: not a custom handle (only an env built with MPOPIS_DEFINE_ENV_TABLE of mpopis_env.h takes a table)"; return MPOPIS_ERR_ARG; }
+    if (!h->custom.has_table) { h->err = "mpopis_set_env_table: the handle's code object has no mpopis_env_table_abi (build the env with MPOPIS_DEFINE_ENV_TABLE)"; return MPOPIS_ERR_ARG; }
+    if (n < 0 || n > MPOPIS_ENV_MAX_TABLE) { h->err = "mpopis_set_env_table: n must be 0.." + std::to_string(MPOPIS_ENV_MAX_TABLE) + " doubles per slot"; return MPOPIS_ERR_ARG; }
+    if (n > 0 && !data) { h->err = "mpopis_set_env_table: data is NULL with n > 0"; return MPOPIS_ERR_ARG; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
+    mpopis::CustomEnv& ce = h->custom;
+    const size_t total = (size_t)n * (per_slot ? (size_t)h->B_full : 1);
+    if (total > ce.table_cap) {
+        double* d = nullptr;
+        HIPCHK(h, hipMalloc((void**)&d, total * sizeof(double)));
+        if (ce.d_table) (void)hipFree(ce.d_table);
+        ce.d_table = d; ce.table_cap = total;
+    }
+    if (total) HIPCHK(h, hipMemcpy(ce.d_table, data, total * sizeof(double), hipMemcpyHostToDevice));
+    ce.ntab = (int)n;
+    ce.table_stride = per_slot ? n : 0;
+    ce.table_view = n ? ce.d_table : nullptr;
     return MPOPIS_OK;
 }
 
@@ -930,6 +980,7 @@ void mpopis_handle::shift_slots(ptrdiff_t db) {
     mv(d_coop_flags, (ptrdiff_t)potrf_coop_flag_words(1, cs)); mv(d_potrf_redo, 1); mv(d_lan_redo, 1);
     mv(d_nesS, nn); mv(d_nesA[0], nn); mv(d_nesA[1], nn); mv(d_nesM, nn); mv(d_nesg, cs); mv(d_nesC, 1); mv(d_nespart, (ptrdiff_t)nes_scatter_workspace_doubles(1, cs, ksplit));
     mv(alive_gate, 1); mv(d_hs, kHarnessDoubles); mv(d_alive, 1); mv(d_actlog, actlog_stride);
+    mv(custom.table_view, (ptrdiff_t)custom.table_stride);                     // a custom env's per-slot tables (stride 0: one shared table)
 }
 
 // pol(env) for all slots.  With >= 2 slots the batch may be split into parts that run as independent chains on

@@ -260,12 +260,14 @@ __global__ void __launch_bounds__(64) k_env_query(EnvDesc env, const double* x, 
 // every kind that is not the car as one of the two simple envs, so a custom handle must never reach them.
 static hipError_t launch_custom_env_kernel(hipFunction_t fn, const EnvDesc& env, const double* x, const int* t, const int* done, const double* action,
                                      double* reward, int* status, const int* alive, int* within, int B, hipStream_t s) {
-    mpopis_env_step_args k{};
+    mpopis_env_step_tab_args kt{};      // (an env with a table: the same fields, then the table; its step / query kernels read it from global memory)
+    mpopis_env_step_args& k = kt.s;
     k.x = (uint64_t)x; k.t = (uint64_t)t; k.done = (uint64_t)done; k.action = (uint64_t)action; k.reward = (uint64_t)reward;
     k.status = (uint64_t)status; k.alive = (uint64_t)alive; k.within = (uint64_t)within; k.params = (uint64_t)env.custom->d_params;
     k.B = B;
     for (int i = 0; i < kMaxAs; ++i) { k.lo[i] = env.lo[i]; k.hi[i] = env.hi[i]; }
-    void* params[] = {&k};
+    kt.table = (uint64_t)env.custom->table_view; kt.table_stride = env.custom->table_stride; kt.ntab = env.custom->ntab;
+    void* params[] = {env.custom->has_table ? (void*)&kt : (void*)&k};
     return hipModuleLaunchKernel(fn, (B + 63) / 64, 1, 1, 64, 1, 1, 0, s, params, nullptr);
 }
 

@@ -520,17 +520,29 @@ static bool launch_car_rollout(const RolloutArgs& a, bool tl, size_t lds, hipStr
 
 // A caller's env (include/mpopis_env.h): the rollout kernel of its code object, same grid as k_rollout_simple.  The built-in kernels treat
 // every kind that is not the car as one of the two simple envs, so a custom handle must never reach them.
+// An env with a table: four-wave workgroups; a table the code object's LDS kernel can stage goes there with ntab * 8 bytes of dynamic LDS (a small
+// table costs no occupancy), a larger one to the kernel that reads it from global memory.
 static bool launch_custom_rollout(const RolloutArgs& a, hipStream_t st, hipError_t* err) {
     const CustomEnv* ce = a.env.custom;
     if (!ce || !ce->rollout) { if (err) *err = hipErrorInvalidHandle; return false; }
-    mpopis_env_rollout_args k{};
+    mpopis_env_rollout_tab_args kt{};
+    mpopis_env_rollout_args& k = kt.r;
     k.x0 = (uint64_t)a.x0; k.t0 = (uint64_t)a.t0; k.done0 = (uint64_t)a.done0; k.Ucur = (uint64_t)a.Ucur; k.Uorig = (uint64_t)a.Uorig;
     k.E = (uint64_t)a.E; k.gvec = (uint64_t)a.gvec; k.cost = (uint64_t)a.cost; k.traj = (uint64_t)a.traj; k.active = (uint64_t)a.active;
     k.iters = (uint64_t)a.iters; k.params = (uint64_t)ce->d_params;
     k.B = a.B; k.K = a.K; k.T = a.T; k.cs = a.cs; k.iter_n = a.iter_n;
     for (int i = 0; i < kMaxAs; ++i) { k.lo[i] = a.env.lo[i]; k.hi[i] = a.env.hi[i]; }
-    void* params[] = {&k};
-    const hipError_t e = hipModuleLaunchKernel(ce->rollout, (a.K + 63) / 64, a.B, 1, 64, 1, 1, 0, st, params, nullptr);
+    hipError_t e;
+    if (ce->has_table) {
+        kt.table = (uint64_t)ce->table_view; kt.table_stride = ce->table_stride; kt.ntab = ce->ntab;
+        const bool lds = ce->ntab <= ce->table_lds_doubles;
+        constexpr int WG = MPOPIS_ENV_TABLE_THREADS;
+        void* params[] = {&kt};
+        e = hipModuleLaunchKernel(lds ? ce->rollout : ce->rollout_gtab, (a.K + WG - 1) / WG, a.B, 1, WG, 1, 1, lds ? (unsigned)ce->ntab * 8u : 0u, st, params, nullptr);
+    } else {
+        void* params[] = {&k};
+        e = hipModuleLaunchKernel(ce->rollout, (a.K + 63) / 64, a.B, 1, 64, 1, 1, 0, st, params, nullptr);
+    }
     if (err) *err = e;
     return e == hipSuccess;
 }

@@ -265,13 +265,23 @@ def pointmass_source():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "env_examples", "pointmass.hip")
 
 
+def mapnav_source():
+    """Path of the example env WITH A TABLE the package ships (env_examples/mapnav.hip: a planar point that follows waypoints across a cost map,
+    SS = 4, AS = 2, NP = 10, table = 2 P waypoint coordinates + a G x G map)."""
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "env_examples", "mapnav.hip")
+
+
 class CustomEnv(_EnvBase):
     """An env of your own under every policy: env(a) and reward(env) are two device functions written against include/mpopis_env.h.
     `code_object_or_source`: the path of a built code object (.hsaco / .co), its bytes, or the path of the source, which is then
     compiled with mpopis_amd.build.build_env (hipcc --genco for gfx950).  `params`: the parameter vector the two functions read;
-    `lo` / `hi`: action_space(env) per action (default [-1, 1]); `reset_state`: what reset!(env) restores (default zeros)."""
+    `lo` / `hi`: action_space(env) per action (default [-1, 1]); `reset_state`: what reset!(env) restores (default zeros).
+    `table`: the data table of an env written with MPOPIS_DEFINE_ENV_TABLE (a path, a map, a lookup curve: the fields a reference env keeps
+    beside its state); every policy made on the env sees it.  `table_per_slot`: the table is (B, n), one row per trial slot of the engine
+    the env is handed to (B = 1 for the env itself and for the policy classes, which run one trial)."""
 
-    def __init__(self, code_object_or_source, state_size, action_size, params=(), lo=None, hi=None, reset_state=None, device=0):
+    def __init__(self, code_object_or_source, state_size, action_size, params=(), lo=None, hi=None, reset_state=None, device=0,
+                 table=None, table_per_slot=False):
         co = code_object_or_source
         if not isinstance(co, (bytes, bytearray)):
             co = os.fspath(co)
@@ -289,8 +299,16 @@ class CustomEnv(_EnvBase):
         self.kind, self.ncars, self.as_, self.ss = "custom", 0, self.action_size, self.state_size
         self.track, self.rng = None, None
         self._eng_device = device
+        self.table, self.table_per_slot = None, bool(table_per_slot)
+        if table is not None:
+            self.table = _f64(table).copy()
         self.reset(_make=False)
         self._mk_engine(device)
+
+    def set_table(self, table, per_slot=False):
+        """Replace the table (None: clear it).  Policies already made on the env keep the table they were made with."""
+        self.table, self.table_per_slot = (None if table is None else _f64(table).copy()), bool(per_slot)
+        self._eng.set_env_table(self.table, per_slot=self.table_per_slot)
 
     def _param_vector(self):
         return self.params
