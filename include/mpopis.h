@@ -59,7 +59,11 @@ extern "C" {
  *    curve), per handle or per trial slot, for custom envs built with MPOPIS_DEFINE_ENV_TABLE of include/mpopis_env.h, whose two functions take
  *    (..., const double *tab, int ntab).  MPOPIS_DEFINE_ENV, its kernels, mpopis_config and every other entry point are unchanged; a library
  *    that predates it does not export the symbol, which is how a caller detects support (its mpopis_create_custom refuses such a code object:
- *    it finds none of the kernels it looks for). */
+ *    it finds none of the kernels it looks for).
+ *    Later gained THREE more entry points, mpopis_set_slot_hyper, mpopis_get_slot_hyper and mpopis_set_Sigma_slots: λ, α, λ_ais, σ (step_factor
+ *    under :nesmppi) and pol.Σ per trial slot, so that one resident batch can sweep them.  mpopis_config and every other entry point are unchanged,
+ *    and a handle that never calls them runs what it ran before; a library that predates them does not export the symbols, which is how a caller
+ *    detects support. */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -112,10 +116,11 @@ typedef struct {
     int32_t ais_its;           /* opt_its / ais_its N (ignored for :mppi/:gmppi)                  */
     int32_t sigma_est;         /* MPOPIS_SIGMA_EST_* (:cemppi)                                    */
     int32_t log_trajectories;  /* params.log: keep K x H x ss model trajectories (MPPI_Logger)   */
+    /* λ, α, λ_ais and cma_sigma hold in every slot until mpopis_set_slot_hyper gives the slots their own */
     double lambda;             /* λ                                                               */
     double alpha;              /* α ; γ = λ(1-α)                                                  */
     double lambda_ais;         /* λ_ais (:μaismppi/:μΣaismppi/:pmcmppi)                           */
-    double elite_threshold;    /* ce_elite_threshold / elite_perc_threshold                       */
+    double elite_threshold;    /* ce_elite_threshold / elite_perc_threshold (always shared)       */
     double cma_sigma;          /* σ (:cmamppi) / step_factor (:nesmppi)                           */
     uint64_t seed;             /* trial slot b draws from seed+b+1 (seed!(pol, seed+k), car_example.jl:188) */
 } mpopis_config;
@@ -180,7 +185,28 @@ int  mpopis_get_state(mpopis_handle *h, double *x /* B*ss */, int32_t *t, int32_
 /* ---- policy state ---------------------------------------------------------------------------- */
 int  mpopis_set_U(mpopis_handle *h, const double *U /* B*cs */);            /* pol.U                */
 int  mpopis_get_U(mpopis_handle *h, double *U /* B*cs */);
-int  mpopis_set_Sigma(mpopis_handle *h, const double *Sigma, int32_t n);    /* pol.Σ : n = as (mppi, or block-replicated :76-78) or cs; col-major, shared by all slots */
+int  mpopis_set_Sigma(mpopis_handle *h, const double *Sigma, int32_t n);    /* pol.Σ : n = as (mppi, or block-replicated :76-78) or cs; col-major, shared by all slots
+                                                                             * (after mpopis_set_Sigma_slots: returns the handle to ONE shared Σ) */
+/* Per-slot policy hyper-parameters and pol.Σ: slot b behaves like a handle created with lambda[b], alpha[b], lambda_ais[b], cma_sigma[b]
+ * and given Sigma[b] through mpopis_set_Sigma (γ_b = λ_b (1 - α_b); :imppi weighs its AIS iterations with λ_b).  They hold for
+ * mpopis_policy_step, mpopis_policy_call, mpopis_run_trials, mpopis_bench_policy_steps and mpopis_rollout_costs (γ_b scales the one
+ * Sigma_inv that call is given).  K, H, N, elite_threshold, the estimator, action bounds and env parameters stay shared.
+ *   mpopis_set_slot_hyper   each pointer is B doubles, or NULL = "the config's value in every slot"; four NULLs return the handle to the
+ *                           shared scalars.  Accepts what mpopis_create accepts for the same fields (MPOPIS_ERR_ARG only for a non-finite
+ *                           step_factor under :nesmppi).  With per-slot lambda_ais, :μΣaismppi on a car env computes the AIS weights in a launch
+ *                           of their own instead of inside the moments kernel (a different summation: last-bits differences).
+ *   mpopis_get_slot_hyper   what is in force, B doubles each; any pointer may be NULL
+ *   mpopis_set_Sigma_slots  B matrices, each n x n col-major, n = as (block-replicated, and the only size for :mppi) or cs, checked per slot
+ *                           like mpopis_set_Sigma: MPOPIS_ERR_ARG "Covariance matrix size problem", MPOPIS_ERR_NOT_PD with the slot number in
+ *                           mpopis_last_error.  The diagonal sampler is used only when EVERY slot's Σ is diagonal.  mpopis_get_Sigma returns each
+ *                           slot's own pol.Σ for the policies that keep Σ fixed.  mpopis_set_Sigma afterwards returns to the shared Σ.
+ * Setup calls like mpopis_set_env_table: they wait for everything the handle has queued before they write; a refused call leaves the handle
+ * as it was; buffers are allocated at the first call (MPOPIS_ERR_HIP when that fails, the handle then stays shared).  After the handle has
+ * returned to the shared values its results are again those of a handle that was never switched. */
+int  mpopis_set_slot_hyper(mpopis_handle *h, const double *lambda, const double *alpha,
+                           const double *lambda_ais, const double *cma_sigma /* σ of :cmamppi, step_factor of :nesmppi */);
+int  mpopis_get_slot_hyper(mpopis_handle *h, double *lambda, double *alpha, double *lambda_ais, double *cma_sigma);
+int  mpopis_set_Sigma_slots(mpopis_handle *h, const double *Sigma /* B*n*n */, int32_t n);
 int  mpopis_seed(mpopis_handle *h, uint64_t seed);                          /* seed!(pol, seed) src/MPOPIS.jl:54 */
 /* Per-slot seeds: slot b draws from seeds[b] (B values).  The reference seeds trial k with seed!(pol, seed + k),
  * src/examples/car_example.jl:187-188; a rank that holds the trials k0, k0+G, k0+2G, ... of a sharded run

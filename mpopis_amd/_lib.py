@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "mpopis_env_query", "mpopis_get_trajectories", "mpopis_set_state_noise", "mpopis_run_trials", "mpopis_timing_enable", "mpopis_timing_read",
     "mpopis_timing_reset", "mpopis_bench_policy_steps",
     "mpopis_create_custom", "mpopis_set_env_table", "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
+    "mpopis_set_slot_hyper", "mpopis_get_slot_hyper", "mpopis_set_Sigma_slots",
 ]
 
 
@@ -73,6 +74,10 @@ def lib():
             L.mpopis_create_custom.argtypes = [C.POINTER(Config), C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(H)]
         if hasattr(L, "mpopis_set_env_table"):
             L.mpopis_set_env_table.argtypes = [H, _dp, C.c_int64, C.c_int32]
+        if hasattr(L, "mpopis_set_slot_hyper"):                 # (per-slot λ, α, λ_ais, σ and Σ: newer than custom envs)
+            L.mpopis_set_slot_hyper.argtypes = [H, _dp, _dp, _dp, _dp]
+            L.mpopis_get_slot_hyper.argtypes = [H, _dp, _dp, _dp, _dp]
+            L.mpopis_set_Sigma_slots.argtypes = [H, _dp, C.c_int32]
         L.mpopis_destroy.argtypes = [H]
         L.mpopis_destroy.restype = None
         L.mpopis_set_env_params.argtypes = [H, _dp, C.c_int32]

@@ -55,7 +55,10 @@ void mpopis_handle::init_cma_constants() {
     const double c[7] = {mu_eff, c_sigma, d_sigma, c_Sigma, c1, c_mu, E_cma};
     for (int i = 0; i < 7; ++i) cma_consts[i] = c[i];
 }
-void mpopis_handle::cma_begin() { launch_cma_begin(d_cma_scal, d_cma_vec, d_sig2, cfg.cma_sigma, cs, B, stream); }
+void mpopis_handle::cma_begin() {
+    if (slot_hyper()) launch_cma_begin_slots(d_cma_scal, d_cma_vec, d_sig2, d_sl_sigma, cs, B, stream);
+    else launch_cma_begin(d_cma_scal, d_cma_vec, d_sig2, cfg.cma_sigma, cs, B, stream);
+}
 const double* mpopis_handle::cma_sigma2() { return d_sig2; }
 
 namespace mpopis {
@@ -95,7 +98,8 @@ int mpopis_handle::ais_update(int n, bool injected) {
         const bool fold = one_pass && weights_in_moments;
         if (!fold) {
             time_begin(3);
-            launch_weights(d_cost, d_w, B, K, lam, d_active, d_status, stream, d_wsum);
+            if (slot_hyper()) launch_weights_slots(d_cost, d_w, B, K, d_sl_nil_ais, d_active, d_status, stream, d_wsum);
+            else launch_weights(d_cost, d_w, B, K, lam, d_active, d_status, stream, d_wsum);
             if (!one_pass) launch_wmean(d_E, d_w, nullptr, nullptr, d_mu, B, cs, K, 1, d_active, stream);     // μ′ (mean(E, pw, dims=2))
             time_end();
         }
@@ -111,7 +115,8 @@ int mpopis_handle::ais_update(int n, bool injected) {
     }
     if (pol == MPOPIS_POL_PMCMPPI) {                                                          // :802-809
         time_begin(3);
-        launch_weights(d_cost, d_w, B, K, cfg.lambda_ais, d_active, d_status, stream);
+        if (slot_hyper()) launch_weights_slots(d_cost, d_w, B, K, d_sl_nil_ais, d_active, d_status, stream);
+        else launch_weights(d_cost, d_w, B, K, cfg.lambda_ais, d_active, d_status, stream);
         time_end();
         time_begin(5);
         launch_alias_build(d_w, d_accept, d_alias, B, K, d_active, stream, d_alias_need, d_alias_stack);                   // Categorical(ws) -> AliasTable
@@ -196,13 +201,13 @@ int mpopis_handle::ais_update(int n, bool injected) {
         time_begin(4);
         const size_t nn = (size_t)cs * cs;
         // Σ^-1 = invcov(MvNormal(Σ′)) of THIS iteration: Σ0^-1 (formed at mpopis_set_Sigma) at n = 1, else from the factor it sampled from
-        const double* S = d_nesS0; size_t Sstride = 0;
+        const double* S = d_nesS0; size_t Sstride = S0stride;
         if (n > 1) { launch_nes_potri(d_L, nn, d_tmpS, d_nesS, B, cs, d_active, stream); S = d_nesS; Sstride = nn; }
-        // A′: pol.A (shared) into the first buffer at n = 1, then ping-pong (never in place)
+        // A′: pol.A (shared, or each slot's own) into the first buffer at n = 1, then ping-pong (never in place)
         const double* Ain = (n == 1) ? d_nesA0 : d_nesA[n & 1];
         double* Aout = d_nesA[(n - 1) & 1];
-        launch_nes_update(d_E, d_cost, d_nespart, ksplit, S, Sstride, d_nesM, d_tmpS, d_nesg, d_nesC, Ain, n == 1 ? 0 : nn, Aout, d_Sig, d_Ucur,
-                          B, cs, K, cfg.cma_sigma, d_active, stream);
+        launch_nes_update(d_E, d_cost, d_nespart, ksplit, S, Sstride, d_nesM, d_tmpS, d_nesg, d_nesC, Ain, n == 1 ? S0stride : nn, Aout, d_Sig, d_Ucur,
+                          B, cs, K, cfg.cma_sigma, d_active, stream, d_sl_nes_a, d_sl_nes_u);
         time_end();
         return MPOPIS_OK;
     }

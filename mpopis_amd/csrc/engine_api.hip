@@ -383,6 +383,7 @@ static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle
     {
         static const int env_fold = [] { const char* e = getenv("MPOPIS_FOLD_WEIGHTS"); return e ? atoi(e) : 1; }();      // 0: keep the separate reweighting launch (A/B)
         h->weights_in_moments = env_fold && cfg->policy == MPOPIS_POL_MUSIGMAAISMPPI && cfg->env_kind == MPOPIS_ENV_CAR && wcov_weights_from_cost_ok(cs, K, h->ksplit);
+        h->fold_weights_cfg = h->weights_in_moments;
     }
     if (cfg->policy == MPOPIS_POL_CMAMPPI) {
         rc |= dalloc(h, &h->d_cma_scal, (size_t)B * 8); rc |= dalloc(h, &h->d_cma_vec, (size_t)B * 3 * cs); rc |= dalloc(h, &h->d_sig2, B);
@@ -398,6 +399,7 @@ static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle
     }
     if (cfg->log_trajectories) rc |= dalloc(h, &h->d_traj, (size_t)B * K * h->T * h->ss);
     if (rc) { g_create_error = h->err; mpopis_destroy(h); return MPOPIS_ERR_HIP; }
+    h->sh_Sigma0 = h->d_Sigma0; h->sh_L0 = h->d_L0; h->sh_L0p = h->d_L0p; h->sh_nesA0 = h->d_nesA0; h->sh_nesS0 = h->d_nesS0;
     launch_rng_tab_init(h->d_rng_tab, h->stream);
     h->h_status.assign(B, 0);
     if (hipHostMalloc((void**)&h->h_pin, sizeof(double) * B * (h->as + 2)) != hipSuccess) h->h_pin = nullptr;
@@ -604,15 +606,22 @@ int mpopis_set_Sigma(mpopis_handle* h, const double* Sigma, int32_t n) {
     for (int j = 0; j < cs && diag; ++j) for (int i = 0; i < cs; ++i) if (i != j && full[(size_t)i + (size_t)j * cs] != 0.0) { diag = false; break; }
     std::vector<double> ds(cs, 0.0);
     if (diag) for (int i = 0; i < cs; ++i) { const double v = full[(size_t)i + (size_t)i * cs]; if (!(v > 0.0)) { h->err = "PosDefException: Sigma"; return MPOPIS_ERR_NOT_PD; } ds[i] = sqrt(v); }
-    h->sigma_diag = diag;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpyAsync(h->d_Sigma0, full.data(), sizeof(double) * cs * cs, hipMemcpyHostToDevice, h->stream));
+    // a handle on per-slot Σ (mpopis_set_Sigma_slots) returns to the shared one: the slots' buffers are in use by whatever is still queued, and
+    // d_dscale keeps their values until this call has succeeded
+    const bool was_slots = h->S0stride != 0;
+    if (was_slots) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
+    } else h->sigma_diag = diag;
+    auto bcast_dscale = [&] { hipLaunchKernelGGL(k_bcast_f64, dim3((cs + 255) / 256), dim3(256), 0, h->stream, h->d_dscale0, h->d_dscale, (size_t)cs, h->B); };
+    HIPCHK(h, hipMemcpyAsync(h->sh_Sigma0, full.data(), sizeof(double) * cs * cs, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_dscale0, ds.data(), sizeof(double) * cs, hipMemcpyHostToDevice, h->stream));
     // per-slot copy for the diagonal-Σ sampler, once per pol.Σ (it used to be re-broadcast by a launch of its own in every AIS iteration)
-    hipLaunchKernelGGL(k_bcast_f64, dim3((cs + 255) / 256), dim3(256), 0, h->stream, h->d_dscale0, h->d_dscale, (size_t)cs, h->B);
+    if (!was_slots) bcast_dscale();
     // factor once: L0 (shared by all slots; the reference refactors the same Σ every call, :307)
     fill_i32(h->d_status, 0, h->B, h->stream);
-    launch_potrf(h->d_Sigma0, 0, h->d_L0, 1, cs, nullptr, h->d_status, nullptr, h->stream, h->potrf_coop(), h->d_L0p, 0);
+    launch_potrf(h->sh_Sigma0, 0, h->sh_L0, 1, cs, nullptr, h->d_status, nullptr, h->stream, h->potrf_coop(), h->sh_L0p, 0);
     HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, wait_stream(h->stream));
     if (h->h_status[0] != 0) { h->err = "PosDefException: Sigma is not positive definite"; return MPOPIS_ERR_NOT_PD; }
@@ -622,16 +631,161 @@ int mpopis_set_Sigma(mpopis_handle* h, const double* Sigma, int32_t n) {
         if (diag) {
             std::vector<double> a0((size_t)cs * cs, 0.0);
             for (int i = 0; i < cs; ++i) a0[(size_t)i * (cs + 1)] = ds[i];
-            HIPCHK(h, hipMemcpyAsync(h->d_nesA0, a0.data(), sizeof(double) * cs * cs, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->sh_nesA0, a0.data(), sizeof(double) * cs * cs, hipMemcpyHostToDevice, h->stream));
         } else {
-            launch_sym_sqrt(h->d_Sigma0, h->d_tmpS, h->d_nesM, h->d_nesA0, h->d_status, cs, h->stream);
+            launch_sym_sqrt(h->sh_Sigma0, h->d_tmpS, h->d_nesM, h->sh_nesA0, h->d_status, cs, h->stream);
         }
-        launch_nes_potri(h->d_L0, 0, h->d_tmpS, h->d_nesS0, 1, cs, nullptr, h->stream);
+        launch_nes_potri(h->sh_L0, 0, h->d_tmpS, h->sh_nesS0, 1, cs, nullptr, h->stream);
         HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, wait_stream(h->stream));
         HIPCHK(h, hipGetLastError());
         if (h->h_status[0] != 0) { h->err = "PosDefException: sqrt(Sigma) has a non-positive eigenvalue"; return MPOPIS_ERR_NOT_PD; }
     }
+    if (was_slots) {
+        h->d_Sigma0 = h->sh_Sigma0; h->d_L0 = h->sh_L0; h->d_L0p = h->sh_L0p; h->d_nesA0 = h->sh_nesA0; h->d_nesS0 = h->sh_nesS0;
+        h->S0stride = 0; h->P0stride = 0; h->sigma_diag = diag;
+        bcast_dscale();
+        HIPCHK(h, wait_stream(h->stream));
+    }
+    return MPOPIS_OK;
+}
+
+// pol.Σ per slot.  Everything is formed in buffers that are scratch outside a policy step (d_tmpS: the B matrices; d_L / d_Lp: their factors and
+// panels; :nesmppi d_nesA[0] / d_nesA[1]: sqrt(Σ_b) and Σ_b^-1, with d_nesM / d_nesS under them) and copied into the slots' own buffers only when every
+// slot has passed, so a refused call leaves the handle as it was.
+int mpopis_set_Sigma_slots(mpopis_handle* h, const double* Sigma, int32_t n) {
+    if (!h || !Sigma) { if (h) h->err = "mpopis_set_Sigma_slots: null argument"; return MPOPIS_ERR_ARG; }
+    const int cs = h->cs, as = h->as, B = h->B_full;
+    const size_t nn = (size_t)cs * cs, pd = sample_trmm_fusable(cs) ? potrf_panel_doubles(cs) : 0;
+    const bool nes = h->cfg.policy == MPOPIS_POL_NESMPPI;
+    if (!((n == cs && h->cfg.policy != MPOPIS_POL_MPPI) || n == as)) { h->err = "Covariance matrix size problem"; return MPOPIS_ERR_ARG; }     // :79
+    std::vector<double> full((size_t)B * nn, 0.0), ds((size_t)B * cs, 0.0);
+    std::vector<char> slot_diag(B, 1);
+    bool diag = true;
+    for (int b = 0; b < B; ++b) {
+        const double* Sb = Sigma + (size_t)b * n * n;
+        double* fb = full.data() + (size_t)b * nn;
+        if (n == cs && h->cfg.policy != MPOPIS_POL_MPPI) memcpy(fb, Sb, sizeof(double) * nn);
+        else
+            for (int t = 0; t < h->T; ++t)
+                for (int j = 0; j < as; ++j)
+                    for (int i = 0; i < as; ++i) fb[(size_t)(t * as + i) + (size_t)(t * as + j) * cs] = Sb[i + (size_t)j * as];
+        for (int j = 0; j < cs && slot_diag[b]; ++j) for (int i = 0; i < cs; ++i) if (i != j && fb[(size_t)i + (size_t)j * cs] != 0.0) { slot_diag[b] = 0; break; }
+        if (slot_diag[b])
+            for (int i = 0; i < cs; ++i) {
+                const double v = fb[(size_t)i * (cs + 1)];
+                if (!(v > 0.0)) { h->err = "PosDefException: Sigma of slot " + std::to_string(b); return MPOPIS_ERR_NOT_PD; }
+                ds[(size_t)b * cs + i] = sqrt(v);
+            }
+        else diag = false;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
+    if (!h->sl_Sigma0) {                                        // first use: the slots' own buffers
+        double* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        const size_t want[5] = {(size_t)B * nn, (size_t)B * nn, (size_t)B * pd, nes ? (size_t)B * nn : 0, nes ? (size_t)B * nn : 0};
+        for (int i = 0; i < 5; ++i)
+            if (want[i] && hipMalloc((void**)&p[i], want[i] * sizeof(double)) != hipSuccess) {
+                (void)hipGetLastError();
+                for (int j = 0; j < i; ++j) if (p[j]) (void)hipFree(p[j]);
+                h->err = "mpopis_set_Sigma_slots: hipMalloc of the per-slot covariance buffers failed";
+                return MPOPIS_ERR_HIP;
+            }
+        for (double* q : p) if (q) h->allocs.push_back(q);
+        h->sl_Sigma0 = p[0]; h->sl_L0 = p[1]; h->sl_L0p = p[2]; h->sl_nesA0 = p[3]; h->sl_nesS0 = p[4];
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_tmpS, full.data(), sizeof(double) * B * nn, hipMemcpyHostToDevice, h->stream));
+    fill_i32(h->d_status, 0, B, h->stream);
+    launch_potrf(h->d_tmpS, nn, h->d_L, B, cs, nullptr, h->d_status, nullptr, h->stream, h->potrf_coop(), pd ? h->d_Lp : nullptr, pd);
+    if (nes) {
+        // pol.A = sqrt(pol.Σ) and invcov(MvNormal(pol.Σ)) per slot, by the rule of mpopis_set_Sigma: closed form for a diagonal slot, else the eigen-solve
+        std::vector<double> a0(nn);
+        for (int b = 0; b < B; ++b) {
+            if (slot_diag[b]) {
+                std::fill(a0.begin(), a0.end(), 0.0);
+                for (int i = 0; i < cs; ++i) a0[(size_t)i * (cs + 1)] = ds[(size_t)b * cs + i];
+                HIPCHK(h, hipMemcpy(h->d_nesA[0] + (size_t)b * nn, a0.data(), sizeof(double) * nn, hipMemcpyHostToDevice));
+            } else {
+                launch_sym_sqrt(h->d_tmpS + (size_t)b * nn, h->d_nesM + (size_t)b * nn, h->d_nesS + (size_t)b * nn, h->d_nesA[0] + (size_t)b * nn, h->d_status + b, cs, h->stream);
+            }
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));             // (d_nesM is the eigen-solves' workspace until here)
+        launch_nes_potri(h->d_L, nn, h->d_nesM, h->d_nesA[1], B, cs, nullptr, h->stream);
+    }
+    HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    for (int b = 0; b < B; ++b)
+        if (h->h_status[b] != 0) { h->err = "PosDefException: Sigma of slot " + std::to_string(b) + " is not positive definite"; return MPOPIS_ERR_NOT_PD; }
+    copy_f64(h->d_tmpS, h->sl_Sigma0, (size_t)B * nn, h->stream);
+    copy_f64(h->d_L, h->sl_L0, (size_t)B * nn, h->stream);
+    if (pd) copy_f64(h->d_Lp, h->sl_L0p, (size_t)B * pd, h->stream);
+    if (nes) { copy_f64(h->d_nesA[0], h->sl_nesA0, (size_t)B * nn, h->stream); copy_f64(h->d_nesA[1], h->sl_nesS0, (size_t)B * nn, h->stream); }
+    HIPCHK(h, hipMemcpyAsync(h->d_dscale, ds.data(), sizeof(double) * B * cs, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    h->d_Sigma0 = h->sl_Sigma0; h->d_L0 = h->sl_L0; h->d_L0p = h->sl_L0p;
+    if (nes) { h->d_nesA0 = h->sl_nesA0; h->d_nesS0 = h->sl_nesS0; }
+    h->S0stride = nn; h->P0stride = pd; h->sigma_diag = diag;
+    return MPOPIS_OK;
+}
+
+// λ, α, λ_ais, σ per slot.  A setup call (it waits for everything queued); the kernels read what is formed here on the host.
+int mpopis_set_slot_hyper(mpopis_handle* h, const double* lambda, const double* alpha, const double* lambda_ais, const double* cma_sigma) {
+    if (!h) return MPOPIS_ERR_ARG;
+    const int B = h->B_full, K = h->K;
+    if (h->cfg.policy == MPOPIS_POL_NESMPPI && cma_sigma)
+        for (int b = 0; b < B; ++b)
+            if (!std::isfinite(cma_sigma[b])) { h->err = "nesmppi: step_factor (cma_sigma) must be finite (slot " + std::to_string(b) + ")"; return MPOPIS_ERR_ARG; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
+    if (!lambda && !alpha && !lambda_ais && !cma_sigma) {       // back to the config's scalars
+        h->sl_host.clear();
+        h->d_sl_nil = h->d_sl_nil_ais = h->d_sl_gamma = h->d_sl_sigma = h->d_sl_nes_a = h->d_sl_nes_u = nullptr;
+        h->sl_any_gamma = false;
+        h->weights_in_moments = h->fold_weights_cfg;
+        return MPOPIS_OK;
+    }
+    if (!h->sl_buf) {
+        double* p = nullptr;
+        if (hipMalloc((void**)&p, sizeof(double) * 6 * B) != hipSuccess) { (void)hipGetLastError(); h->err = "mpopis_set_slot_hyper: hipMalloc of the per-slot value arrays failed"; return MPOPIS_ERR_HIP; }
+        h->allocs.push_back(p);
+        h->sl_buf = p;
+    }
+    std::vector<double> host((size_t)4 * B), dev((size_t)6 * B);
+    bool any_gamma = false;
+    for (int b = 0; b < B; ++b) {
+        const double lam = lambda ? lambda[b] : h->cfg.lambda, al = alpha ? alpha[b] : h->cfg.alpha;
+        const double la = lambda_ais ? lambda_ais[b] : h->cfg.lambda_ais, sg = cma_sigma ? cma_sigma[b] : h->cfg.cma_sigma;
+        host[b] = lam; host[(size_t)B + b] = al; host[(size_t)2 * B + b] = la; host[(size_t)3 * B + b] = sg;
+        const double gm = lam * (1 - al);
+        any_gamma |= gm != 0.0;
+        dev[b] = -1 / lam;
+        dev[(size_t)B + b] = -1 / (h->cfg.policy == MPOPIS_POL_IMPPI ? lam : la);      // :362 / :647,:712
+        dev[(size_t)2 * B + b] = gm;
+        dev[(size_t)3 * B + b] = sg;
+        dev[(size_t)4 * B + b] = -sg / ((double)K * K);
+        dev[(size_t)5 * B + b] = sg / K;
+    }
+    HIPCHK(h, hipMemcpy(h->sl_buf, dev.data(), sizeof(double) * 6 * B, hipMemcpyHostToDevice));
+    h->sl_host.swap(host);
+    h->d_sl_nil = h->sl_buf; h->d_sl_nil_ais = h->sl_buf + B; h->d_sl_gamma = h->sl_buf + 2 * (size_t)B; h->d_sl_sigma = h->sl_buf + 3 * (size_t)B;
+    h->d_sl_nes_a = h->sl_buf + 4 * (size_t)B; h->d_sl_nes_u = h->sl_buf + 5 * (size_t)B;
+    h->sl_any_gamma = any_gamma;
+    // per-slot λ_ais leaves the fused "weights inside the moments kernel" form (its -1/λ_ais is one scalar): the path MPOPIS_FOLD_WEIGHTS=0 selects
+    h->weights_in_moments = h->fold_weights_cfg && !lambda_ais;
+    return MPOPIS_OK;
+}
+
+int mpopis_get_slot_hyper(mpopis_handle* h, double* lambda, double* alpha, double* lambda_ais, double* cma_sigma) {
+    if (!h) return MPOPIS_ERR_ARG;
+    const int B = h->B_full;
+    double* out[4] = {lambda, alpha, lambda_ais, cma_sigma};
+    const double cfgv[4] = {h->cfg.lambda, h->cfg.alpha, h->cfg.lambda_ais, h->cfg.cma_sigma};
+    for (int i = 0; i < 4; ++i)
+        if (out[i]) for (int b = 0; b < B; ++b) out[i][b] = h->sl_host.empty() ? cfgv[i] : h->sl_host[(size_t)i * B + b];
     return MPOPIS_OK;
 }
 
@@ -665,7 +819,7 @@ int mpopis_get_Sigma(mpopis_handle* h, double* out) {
     // d_tmpS is scratch outside a policy step
     const double* scale = (pol == MPOPIS_POL_CMAMPPI && h->N > 1) ? h->d_sig2 : nullptr;     // MvNormal(σ²Σ′) :550-554
     hipLaunchKernelGGL(k_scaled_copy_f64, dim3((nn + 255) / 256, h->B), dim3(256), 0, h->stream,
-                       sigma_fixed ? h->d_Sigma0 : h->d_Sig, sigma_fixed ? (size_t)0 : nn, scale, h->d_tmpS, nn);
+                       sigma_fixed ? h->d_Sigma0 : h->d_Sig, sigma_fixed ? h->S0stride : nn, scale, h->d_tmpS, nn);
     HIPCHK(h, hipMemcpyAsync(out, h->d_tmpS, sizeof(double) * h->B * nn, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, wait_stream(h->stream));
     return MPOPIS_OK;
@@ -675,7 +829,7 @@ int mpopis_rollout_costs(mpopis_handle* h, const double* x0, const double* U, co
                          const double* Sigma_inv, double* cost) {
     if (!h || !U || !E || !cost) return MPOPIS_ERR_ARG;
     if (h->env.kind == MPOPIS_ENV_CAR && h->env.track.P == 0) { h->err = "track not set"; return MPOPIS_ERR_ARG; }
-    if (h->gamma != 0.0 && !Sigma_inv) { h->err = "Sigma_inv required when alpha != 1"; return MPOPIS_ERR_ARG; }
+    if (h->use_gvec() && !Sigma_inv) { h->err = "Sigma_inv required when alpha != 1"; return MPOPIS_ERR_ARG; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, K = h->K, cs = h->cs;
     if (x0) HIPCHK(h, hipMemcpyAsync(h->d_x, x0, sizeof(double) * B * h->ss, hipMemcpyHostToDevice, h->stream));
@@ -684,9 +838,10 @@ int mpopis_rollout_costs(mpopis_handle* h, const double* x0, const double* U, co
     HIPCHK(h, hipMemcpyAsync(h->d_Z, E, sizeof(double) * B * cs * K, hipMemcpyHostToDevice, h->stream));
     launch_transpose_in(h->d_Z, h->d_E, B, cs, K, h->stream);
     const double* gv = nullptr;
-    if (h->gamma != 0.0) {
+    if (h->use_gvec()) {
         HIPCHK(h, hipMemcpyAsync(h->d_tmpS, Sigma_inv, sizeof(double) * cs * cs, hipMemcpyHostToDevice, h->stream));
-        launch_gvec_from_inv(h->d_tmpS, h->d_Uin, h->gamma, h->d_gvec, B, cs, h->stream);
+        if (h->slot_hyper()) launch_gvec_from_inv_slots(h->d_tmpS, h->d_Uin, h->d_sl_gamma, h->d_gvec, B, cs, h->stream);
+        else launch_gvec_from_inv(h->d_tmpS, h->d_Uin, h->gamma, h->d_gvec, B, cs, h->stream);
         gv = h->d_gvec;
     }
     fill_i32(h->d_status, 0, B, h->stream);
@@ -980,6 +1135,8 @@ void mpopis_handle::shift_slots(ptrdiff_t db) {
     mv(d_coop_flags, (ptrdiff_t)potrf_coop_flag_words(1, cs)); mv(d_potrf_redo, 1); mv(d_lan_redo, 1);
     mv(d_nesS, nn); mv(d_nesA[0], nn); mv(d_nesA[1], nn); mv(d_nesM, nn); mv(d_nesg, cs); mv(d_nesC, 1); mv(d_nespart, (ptrdiff_t)nes_scatter_workspace_doubles(1, cs, ksplit));
     mv(alive_gate, 1); mv(d_hs, kHarnessDoubles); mv(d_alive, 1); mv(d_actlog, actlog_stride);
+    mv(d_Sigma0, (ptrdiff_t)S0stride); mv(d_L0, (ptrdiff_t)S0stride); mv(d_L0p, (ptrdiff_t)P0stride); mv(d_nesA0, (ptrdiff_t)S0stride); mv(d_nesS0, (ptrdiff_t)S0stride);   // per-slot pol.Σ (stride 0: shared)
+    mv(d_sl_nil, 1); mv(d_sl_nil_ais, 1); mv(d_sl_gamma, 1); mv(d_sl_sigma, 1); mv(d_sl_nes_a, 1); mv(d_sl_nes_u, 1);          // per-slot λ, α, λ_ais, σ (null: the scalars)
     mv(custom.table_view, (ptrdiff_t)custom.table_stride);                     // a custom env's per-slot tables (stride 0: one shared table)
 }
 
@@ -1155,7 +1312,10 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
     // status / active / iters reset, U_orig = pol.U (d_Uin keeps U_orig; d_Ucur is the rebinding pol.U inside the loop), extended start states
     launch_step_begin(status_sticky ? nullptr : d_status, d_active, alive_gate, d_iters, d_U, d_Uin, d_Ucur, B, cs,
                       env.kind == MPOPIS_ENV_CAR ? d_x : nullptr, d_xext, env.ncars, stream, weights_in_moments ? d_cmin : nullptr, env.track, d_iters_acc);
-    if (!sigma_fixed) hipLaunchKernelGGL(k_bcast_f64, dim3((nn + 255) / 256), dim3(256), 0, stream, d_Sigma0, d_Sig, nn, B);   // Σ′ = pol.Σ
+    if (!sigma_fixed) {                                                                                                          // Σ′ = pol.Σ
+        if (S0stride) copy_f64(d_Sigma0, d_Sig, (size_t)B * nn, stream);                                                          // (each slot's own)
+        else hipLaunchKernelGGL(k_bcast_f64, dim3((nn + 255) / 256), dim3(256), 0, stream, d_Sigma0, d_Sig, nn, B);
+    }
     if (pol == MPOPIS_POL_CMAMPPI) cma_begin();
     // Shapes the fused sampler does not cover (cs > 128: Z goes through memory anyway) with device RNG, a dense proposal from iteration 2 on
     // and the handle's other streams free: prefetch Z on a side stream (see below).  For fusable shapes the prefetch was measured and LOSES
@@ -1178,7 +1338,8 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
         // a numerically singular factor one iteration later -- factoring the unscaled Σ′ flipped exactly that in test_cma_posdef_error_matches_reference_behaviour.
         const bool cma_scaled = pol == MPOPIS_POL_CMAMPPI && N > 1;
         const double* osc2 = (cma_scaled && n == 1) ? cma_sigma2() : nullptr;
-        if (sigma_fixed || n == 1) { Lp = d_L0; Lstride = 0; }
+        const bool own_factor = !(sigma_fixed || n == 1);      // this iteration factors its own Σ′ (else: the factor of pol.Σ, shared or per slot)
+        if (!own_factor) { Lp = d_L0; Lstride = S0stride; }
         else {
             time_begin(2);
             launch_potrf(d_Sig, nn, d_L, B, cs, cma_scaled ? cma_sigma2() : nullptr, d_status, d_active, stream, potrf_coop(), d_Lp, potrf_panel_doubles(cs));
@@ -1186,7 +1347,10 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
             Lp = d_L; Lstride = nn;
         }
         cur_L = Lp; cur_Lstride = Lstride; cur_L_scaled = cma_scaled && n > 1;
-        if (gamma != 0.0) launch_chol_solve_gvec(Lp, Lstride, d_Uin, gamma, d_gvec, B, cs, d_active, stream, osc2);
+        if (use_gvec()) {
+            if (slot_hyper()) launch_chol_solve_gvec_slots(Lp, Lstride, d_Uin, d_sl_gamma, d_gvec, B, cs, d_active, stream, osc2);
+            else launch_chol_solve_gvec(Lp, Lstride, d_Uin, gamma, d_gvec, B, cs, d_active, stream, osc2);
+        }
         // ---- E = rand(rng, P, K) ----------------------------------------------------------------
         time_begin(1);
         if (first_diag && !(pol == MPOPIS_POL_CMAMPPI)) dsc = d_dscale;        // sqrt(diag Σ) per slot, written by mpopis_set_Sigma
@@ -1205,7 +1369,7 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
         } else if (!dsc && pol != MPOPIS_POL_MPPI) {
             // dense proposal: draw inside the unwhitening kernel when the shape allows it (no Z round trip through HBM)
             fused = launch_sample_trmm_fused(Lp, Lstride, d_E, B, cs, K, d_seeds, (uint32_t)mpc_step, (uint32_t)(n - 1), d_active, stream, d_rng_tab,
-                                             Lstride ? d_Lp : d_L0p, Lstride ? potrf_panel_doubles(cs) : (size_t)0, osc2);
+                                             own_factor ? d_Lp : d_L0p, own_factor ? potrf_panel_doubles(cs) : P0stride, osc2);
             if (!fused) launch_sample_normal(Zdst, B, cs, K, as, 0, d_seeds, (uint32_t)mpc_step, (uint32_t)(n - 1), dsc, d_active, stream, d_rng_tab);
         } else {
             launch_sample_normal(Zdst, B, cs, K, as, pol == MPOPIS_POL_MPPI, d_seeds, (uint32_t)mpc_step, (uint32_t)(n - 1), dsc, d_active, stream, d_rng_tab);
@@ -1232,7 +1396,7 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
         }
         if (n == 1 && record_after_first_sampler) (void)hipEventRecord(record_after_first_sampler, stream);   // the next part starts when this one enters its first rollout
         // ---- trajectory_cost = simulate_model(pol, env, E, Σ_inv, U_orig) -------------------------
-        rollout(d_Ucur, d_Uin, gamma != 0.0 ? d_gvec : nullptr, d_active, d_iters, n);   // also records iters_run = n for the active slots
+        rollout(d_Ucur, d_Uin, use_gvec() ? d_gvec : nullptr, d_active, d_iters, n);   // also records iters_run = n for the active slots
         fork_recorded = false;
         if (z_prefetch_ok && n < N) {
             // Z of iteration n+1 depends on nothing but (seed, MPC step, iteration): draw it now, beside the latency-bound kernels that follow
@@ -1252,7 +1416,8 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
     }
     // weights = compute_weights(IT(λ), cost); weighted_noise = Σ_k w_k (E_k + (pol.U - U_orig)); roll
     time_begin(3);
-    launch_weights(d_cost, d_w, B, K, cfg.lambda, alive_gate, d_status, stream);
+    if (slot_hyper()) launch_weights_slots(d_cost, d_w, B, K, d_sl_nil, alive_gate, d_status, stream);
+    else launch_weights(d_cost, d_w, B, K, cfg.lambda, alive_gate, d_status, stream);
     launch_wmean(d_E, d_w, d_Ucur, d_Uin, d_wn, B, cs, K, 0, alive_gate, stream);
     launch_finalize_env(d_wn, d_U, d_control, B, cs, as, T, env, stream);
     time_end();

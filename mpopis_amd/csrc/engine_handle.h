@@ -34,7 +34,23 @@ struct mpopis_handle {
     double *d_Sigma0 = nullptr, *d_L0 = nullptr, *d_dscale0 = nullptr;   // shared pol.Σ, its factor, sqrt(diag)
     double *d_Sig = nullptr, *d_L = nullptr, *d_tmpS = nullptr, *d_dscale = nullptr;
     double *d_L0p = nullptr, *d_Lp = nullptr;     // the factors once more in the fused sampler's staging layout (potrf_panel_doubles(cs) per matrix; cs <= 128)
-    bool sigma_diag = false;
+    bool sigma_diag = false;                      // pol.Σ diagonal (per-slot Σ: in every slot); d_dscale then holds each slot's sqrt(diag)
+    // Per-slot pol.Σ (mpopis_set_Sigma_slots).  d_Sigma0 / d_L0 / d_L0p / d_nesA0 / d_nesS0 above are what is IN FORCE: the shared buffers
+    // (sh_*, stride 0) until the first call, then the [B] copies (sl_*, allocated by that call; strides cs² and the panel size), moved with the
+    // slot views.  mpopis_set_Sigma points them back at the shared buffers.
+    size_t S0stride = 0, P0stride = 0;
+    double *sh_Sigma0 = nullptr, *sh_L0 = nullptr, *sh_L0p = nullptr, *sh_nesA0 = nullptr, *sh_nesS0 = nullptr;
+    double *sl_Sigma0 = nullptr, *sl_L0 = nullptr, *sl_L0p = nullptr, *sl_nesA0 = nullptr, *sl_nesS0 = nullptr;
+    // Per-slot λ, α, λ_ais, σ (mpopis_set_slot_hyper).  sl_host: the four arrays in force ([4][B], empty = the config's scalars in every slot);
+    // the device arrays hold what the kernels consume, formed on the host like the scalars they replace: -1/λ_b, -1/λ_ais,b (-1/λ_b under :imppi),
+    // γ_b, σ_b, and for :nesmppi -sf_b/K² and sf_b/K.  Null while the handle runs on the scalars; moved with the slot views.
+    std::vector<double> sl_host;
+    double* sl_buf = nullptr;                     // one allocation of 6 B doubles behind the six views
+    double *d_sl_nil = nullptr, *d_sl_nil_ais = nullptr, *d_sl_gamma = nullptr, *d_sl_sigma = nullptr, *d_sl_nes_a = nullptr, *d_sl_nes_u = nullptr;
+    bool sl_any_gamma = false;
+    bool slot_hyper() const { return d_sl_nil != nullptr; }
+    bool use_gvec() const { return slot_hyper() ? sl_any_gamma : gamma != 0.0; }      // γ U' Σ^-1 E enters the cost in some slot
+    bool fold_weights_cfg = false;                // what weights_in_moments is while λ_ais is the config's scalar
     // samples / costs / weights
     double *d_Z = nullptr, *d_E = nullptr, *d_Zin = nullptr, *d_cost = nullptr, *d_w = nullptr;
     unsigned long long* d_cmin = nullptr;   // [B] running minimum cost of the last rollout launch (cost_key), when the AIS reweighting is folded into the moments kernel

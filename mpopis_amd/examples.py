@@ -5,6 +5,7 @@ gather of the per-trial summary records (mpopis_gather_summary behind the C ABI 
 nccl == RCCL; torch.distributed's own gather for the gloo CPU tests).  Prints the reference's tables."""
 import math
 import time
+import warnings
 import numpy as np
 
 from .engine import Engine
@@ -73,6 +74,36 @@ def shard_trials(num_trials, rank, world):
     return [k for k in range(1, num_trials + 1) if (k - 1) % world == rank]
 
 
+def split_per_trial(value, num_trials, rank=0, world=1, cov=False):
+    """What one rank passes for a keyword that may be given per trial.  Returns (shared, per_slot), one of them None:
+    a scalar (cov: a vector = one diagonal, or a square matrix) keeps its meaning and comes back as `shared`; a sequence of length num_trials
+    (cov: num_trials vectors or matrices; an array that is square in 2-D is ONE matrix, so pass (num_trials, n, n) when num_trials == n) gives
+    trial k (1-based) entry k - 1, and `per_slot` holds the entries of this rank's trials (shard_trials) in slot order.
+    A scalar keyword takes a scalar or a 1-D sequence and nothing else.  A square 2-D cov with num_trials rows that is not symmetric cannot be
+    one covariance matrix and was most likely meant as per-trial diagonals: it is still read as one matrix, as before, with a warning."""
+    a = np.asarray(value, dtype=np.float64)
+    shared_ndim = 1 if cov else 0
+    if not cov and a.ndim > 1:
+        raise ValueError("a per-trial value is a scalar or one value per trial (%d), got shape %s" % (num_trials, a.shape))
+    if a.ndim <= shared_ndim or (cov and a.ndim == 2 and a.shape[0] == a.shape[1]):
+        if cov and a.ndim == 2 and a.shape[0] == num_trials and num_trials > 1 and not np.array_equal(a, a.T):
+            warnings.warn("cov_mat of shape %s is read as ONE matrix for all %d trials although it is not symmetric; per-trial diagonals of this "
+                          "size go as shape (%d, %d, %d)" % (a.shape, num_trials, num_trials, a.shape[1], a.shape[1]), stacklevel=3)
+        return value, None
+    if a.ndim > shared_ndim + 2 or a.shape[0] != num_trials:
+        raise ValueError("a per-trial value needs one entry per trial (%d), got shape %s" % (num_trials, a.shape))
+    return None, a[[k - 1 for k in shard_trials(num_trials, rank, world)]]
+
+
+def _apply_per_trial(eng, per, cov_slots, policy):
+    """Engine.set_slot_hyper / set_Sigma_slots from the per_slot halves of split_per_trial (None: that keyword is shared)."""
+    if any(v is not None for v in per.values()):
+        eng.set_slot_hyper(lam=per["λ"], alpha=per["α"], lam_ais=per["λ_ais"],
+                           **{"step_factor" if policy == "nesmppi" else "cma_sigma": per["cma_σ"]})
+    if cov_slots is not None:
+        eng.set_Sigma_slots(cov_slots)
+
+
 def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="cemppi", laps=2, num_samples=150, horizon=50,
                         λ=10.0, α=1.0, U0=None, cov_mat=None, ais_its=10, λ_ais=20.0, ce_elite_threshold=0.8, ce_Σ_est="ss",
                         cma_σ=0.75, cma_elite_threshold=0.8, state_x_sigma=0.0, state_y_sigma=0.0, state_ψ_sigma=0.0,
@@ -80,6 +111,8 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
     """Returns (records, summary) on rank 0 (None elsewhere).  Differences from the reference harness, all
     forced by the platform: plotting/GIF options are not offered (out of scope); the state noise (single car only,
     car_example.jl:224-236) is drawn from the trial's device stream instead of the env's MersenneTwister.
+    λ, α, λ_ais and cma_σ also take a sequence of num_trials values, and cov_mat a sequence of num_trials vectors or matrices
+    (split_per_trial): trial k runs with entry k - 1, all trials of a rank still in one resident batch -- a hyper-parameter sweep in one call.
     ce_Σ_est defaults to :ss like the reference (car_example.jl:66); :mle is the other supported estimator."""
     pt = str(policy_type).lstrip(":")
     rank = dist.get_rank() if (dist is not None and dist.is_initialized()) else 0
@@ -93,14 +126,20 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
         dist.broadcast_object_list(sd, src=0)
         seed = sd[0]
     mine = shard_trials(num_trials, rank, world)
+    kw = {"λ": λ, "α": α, "λ_ais": λ_ais, "cma_σ": cma_σ}
+    split = {k: split_per_trial(v, num_trials, rank, world) for k, v in kw.items()}
+    # (the handle's own scalar of a per-trial keyword is never in force: trial 1's entry stands in for it at create)
+    λ, α, λ_ais, cma_σ = [v if split[k][1] is None else float(np.asarray(v, dtype=np.float64)[0]) for k, v in kw.items()]
+    cov_shared, cov_slots = split_per_trial(cov_mat, num_trials, rank, world, cov=True)
     t0 = time.time()
     # every rank keeps a handle (even with no trials: it takes part in the collective); all of a rank's trials
     # k0, k0+G, ... live in ONE resident batch, slot i seeded like the reference's trial k_i: seed!(pol, seed + k) (:187-188)
     eng = Engine("car", num_cars, pt, num_samples, horizon, batch=max(len(mine), 1), lam=λ, alpha=α, ais_its=ais_its, lam_ais=λ_ais,
                  elite_threshold=(cma_elite_threshold if pt == "cmamppi" else ce_elite_threshold), sigma_est=str(ce_Σ_est).lstrip(":"),
-                 cma_sigma=cma_σ, seed=seed, device=device, cov=cov_mat, U0=U0)
+                 cma_sigma=cma_σ, seed=seed, device=device, cov=cov_shared, U0=U0)
     r = np.zeros((0, RECORD_LEN))
     if mine:
+        _apply_per_trial(eng, {k: v[1] for k, v in split.items()}, cov_slots, pt)
         eng.seed_slots([seed + k for k in mine])
         eng.set_state_noise(state_x_sigma, state_y_sigma, state_ψ_sigma)
         r = eng.run_trials(num_steps, laps)
@@ -146,9 +185,15 @@ def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cem
     pt = str(policy_type).lstrip(":")
     if seed is None:
         seed = int(np.random.default_rng().integers(1, 10 ** 10))
+    kw = {"λ": λ, "α": α, "λ_ais": λ_ais, "cma_σ": cma_σ}
+    split = {k: split_per_trial(v, num_trials) for k, v in kw.items()}              # per-trial values: see simulate_car_racing
+    λ, α, λ_ais, cma_σ = [v if split[k][1] is None else float(np.asarray(v, dtype=np.float64)[0]) for k, v in kw.items()]
+    cov_shared, cov_slots = split_per_trial(cov_mat, num_trials, cov=True)
     eng = Engine(env_kind, 0, pt, num_samples, horizon, batch=num_trials, lam=λ, alpha=α, ais_its=ais_its, lam_ais=λ_ais,
                  elite_threshold=(cma_elite_threshold if pt == "cmamppi" else ce_elite_threshold), sigma_est=str(ce_Σ_est).lstrip(":"),
-                 cma_sigma=cma_σ, seed=seed, device=device, cov=np.asarray(cov_mat, dtype=np.float64), U0=np.asarray(U0, dtype=np.float64))
+                 cma_sigma=cma_σ, seed=seed, device=device, cov=None if cov_shared is None else np.asarray(cov_shared, dtype=np.float64),
+                 U0=np.asarray(U0, dtype=np.float64))
+    _apply_per_trial(eng, {k: v[1] for k, v in split.items()}, cov_slots, pt)
     if x0 is not None:
         eng.set_state(np.asarray(x0, dtype=np.float64).reshape(num_trials, ss))
     t0 = time.time()
