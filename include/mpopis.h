@@ -186,7 +186,10 @@ int  mpopis_get_state(mpopis_handle *h, double *x /* B*ss */, int32_t *t, int32_
 int  mpopis_set_U(mpopis_handle *h, const double *U /* B*cs */);            /* pol.U                */
 int  mpopis_get_U(mpopis_handle *h, double *U /* B*cs */);
 int  mpopis_set_Sigma(mpopis_handle *h, const double *Sigma, int32_t n);    /* pol.Σ : n = as (mppi, or block-replicated :76-78) or cs; col-major, shared by all slots
-                                                                             * (after mpopis_set_Sigma_slots: returns the handle to ONE shared Σ) */
+                                                                             * (after mpopis_set_Sigma_slots: returns the handle to ONE shared Σ).
+                                                                             * A refused call (size, not positive definite) leaves the handle as it was:
+                                                                             * the Σ in force, its factor and the sampler's scales are replaced only
+                                                                             * once the new matrix has passed every check. */
 /* Per-slot policy hyper-parameters and pol.Σ: slot b behaves like a handle created with lambda[b], alpha[b], lambda_ais[b], cma_sigma[b]
  * and given Sigma[b] through mpopis_set_Sigma (γ_b = λ_b (1 - α_b); :imppi weighs its AIS iterations with λ_b).  They hold for
  * mpopis_policy_step, mpopis_policy_call, mpopis_run_trials, mpopis_bench_policy_steps and mpopis_rollout_costs (γ_b scales the one

@@ -134,18 +134,21 @@ __device__ __forceinline__ void status_raise(int* p, int code) {
     }
 }
 
+// A quantity that is one number for the whole batch or one per trial slot (mpopis_set_slot_hyper).  A kernel that consumes one is a template
+// over the type of that one argument -- double, or const double* indexed by the slot -- so both forms come from one body.
+__device__ __forceinline__ double slot_val(double v, int) { return v; }
+__device__ __forceinline__ double slot_val(const double* v, int b) { return v[b]; }
+struct SlotVal { double v; const double* per_slot; };   // per_slot == nullptr: v in every slot; else per_slot[b] (a [B] device array that moves with the slot views)
+
 bool launch_rollout(const RolloutArgs& a, hipStream_t s, hipError_t* custom_err = nullptr);      // false: nothing launched -- no rollout kernel for this env, or the custom env's launch failed (*custom_err says why)
 void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t s, const Track& tk);
 // (iters_acc: per-slot running sum of the iteration counts of earlier steps, folded in before iters is cleared; may be null)
 void launch_step_begin(int* status, int* active, const int* alive, int* iters, const double* U, double* Uin, double* Ucur, int B, int cs,
                        const double* x, double* xext, int ncars, hipStream_t st, unsigned long long* cmin, const Track& tk, unsigned long long* iters_acc = nullptr);
 
-// compute_weights (utils.jl:79-86) per slot: w = exp(-(1/λ)(c-min c)) / Σ
-void launch_weights(const double* cost, double* w, int B, int K, double lambda, const int* active,
+// compute_weights (utils.jl:79-86) per slot: w = exp(-(1/λ)(c-min c)) / Σ, given -1/λ
+void launch_weights(const double* cost, double* w, int B, int K, SlotVal neg_inv_lambda, const int* active,
                     int* status, hipStream_t s, double* wsum = nullptr);
-// the same with -1/λ_b per slot (neg_inv_lambda [B], mpopis_set_slot_hyper); same forms, same launch shape
-void launch_weights_slots(const double* cost, double* w, int B, int K, const double* neg_inv_lambda, const int* active,
-                          int* status, hipStream_t s, double* wsum = nullptr);
 // which form of k_weights launch_weights runs for K samples (the workgroup size decides: the register form covers K <= 8 x blockDim)
 enum WeightsForm { WEIGHTS_REG_256 = 0, WEIGHTS_REG_1024 = 1, WEIGHTS_3PASS_1024 = 2 };
 int weights_block(int K);
@@ -206,13 +209,9 @@ constexpr int kPanelRows = 128;
 size_t potrf_panel_doubles(int n);
 void launch_potrf(const double* A, size_t Astride, double* L, int B, int n, const double* scale, int* status, int* active, hipStream_t s,
                   const CoopCtx& coop = CoopCtx(), double* panel = nullptr, size_t pstride = 0);
-void launch_chol_solve_gvec(const double* L, size_t Lstride, const double* Uorig, double gamma, double* g, int B, int n, const int* active, hipStream_t s,
+void launch_chol_solve_gvec(const double* L, size_t Lstride, const double* Uorig, SlotVal gamma, double* g, int B, int n, const int* active, hipStream_t s,
                             const double* inv_scale2 = nullptr);      // L = chol(Σ) while the proposal is MvNormal(s²Σ) (:cmamppi): g = (s²Σ)^-1 γU = Σ^-1 γU / s²
-void launch_gvec_from_inv(const double* Sinv, const double* Uorig, double gamma, double* g, int B, int n, hipStream_t s);
-// per-slot γ_b (gamma [B]): the forms a handle with per-slot λ / α runs (mpopis_set_slot_hyper)
-void launch_chol_solve_gvec_slots(const double* L, size_t Lstride, const double* Uorig, const double* gamma, double* g, int B, int n, const int* active, hipStream_t s,
-                                  const double* inv_scale2 = nullptr);
-void launch_gvec_from_inv_slots(const double* Sinv, const double* Uorig, const double* gamma, double* g, int B, int n, hipStream_t s);
+void launch_gvec_from_inv(const double* Sinv, const double* Uorig, SlotVal gamma, double* g, int B, int n, hipStream_t s);
 // :nesmppi (kernels_nes.hip; kernels_invsqrt.hip for the square root)
 void launch_nes_break(const double* cost, int B, int K, int* active, int* status, hipStream_t s);
 size_t nes_scatter_workspace_doubles(int B, int cs, int ksplit);
@@ -221,8 +220,7 @@ void launch_nes_scatter(const double* E, const double* cost, double* part, doubl
 void launch_nes_potri(const double* L, size_t Lstride, double* X, double* S, int B, int n, const int* active, hipStream_t s);
 void launch_nes_update(const double* E, const double* cost, double* part, int ksplit, const double* S, size_t Sstride, double* M, double* T,
                        double* g, double* Csum, const double* Ain, size_t Astride, double* Aout, double* Sig, double* U,
-                       int B, int cs, int K, double step_factor, const int* active, hipStream_t s,
-                       const double* a_scale = nullptr /* [B] -sf_b / K² */, const double* u_scale = nullptr /* [B] sf_b / K: per-slot step_factor instead of the scalar */);
+                       int B, int cs, int K, SlotVal a_scale /* -sf / K² */, SlotVal u_scale /* sf / K */, const int* active, hipStream_t s);
 void launch_sym_sqrt(const double* A, double* M, double* V, double* out, int* status, int n, hipStream_t s);
 // kernels_mfma.hip
 void launch_trmm_LZ_mfma(const double* L, size_t Lstride, const double* Z, double* E, int B, int n, int K, const int* active, hipStream_t s,
@@ -301,8 +299,7 @@ void launch_lanczos_invsqrt(const double* A, const double* prep, const double* b
                             int regions_per_slot = 1, const CoopCtx& coop = CoopCtx());
 size_t invsqrt_coop_words(int B, int n);
 
-void launch_cma_begin(double* scal, double* vec, double* sig2, double sigma0, int cs, int B, hipStream_t s);
-void launch_cma_begin_slots(double* scal, double* vec, double* sig2, const double* sigma0 /* [B] */, int cs, int B, hipStream_t s);
+void launch_cma_begin(double* scal, double* vec, double* sig2, SlotVal sigma0, int cs, int B, hipStream_t s);
 void launch_cma_paths(const double* Cdw, const double* fro, const double* E, const int32_t* order, const double* ws, double* Ucur, double* scal, double* vec,
                       double* sig2, int B, int cs, int K, int n_iter, const double* consts7, int m_elite, const int* active, hipStream_t s);
 void launch_cma_sigma_update(double* Sig, const double* scal, const double* vec, int B, int cs, const double* consts7, int m_elite,

@@ -56,8 +56,7 @@ void mpopis_handle::init_cma_constants() {
     for (int i = 0; i < 7; ++i) cma_consts[i] = c[i];
 }
 void mpopis_handle::cma_begin() {
-    if (slot_hyper()) launch_cma_begin_slots(d_cma_scal, d_cma_vec, d_sig2, d_sl_sigma, cs, B, stream);
-    else launch_cma_begin(d_cma_scal, d_cma_vec, d_sig2, cfg.cma_sigma, cs, B, stream);
+    launch_cma_begin(d_cma_scal, d_cma_vec, d_sig2, sv_sigma(), cs, B, stream);
 }
 const double* mpopis_handle::cma_sigma2() { return d_sig2; }
 
@@ -90,7 +89,6 @@ void launch_add_active(const double* x, double* y, int B, int n, const int* acti
 int mpopis_handle::ais_update(int n, bool injected) {
     const int pol = cfg.policy;
     if (pol == MPOPIS_POL_IMPPI || pol == MPOPIS_POL_MUAISMPPI || pol == MPOPIS_POL_MUSIGMAAISMPPI) {
-        const double lam = (pol == MPOPIS_POL_IMPPI) ? cfg.lambda : cfg.lambda_ais;          // :362 / :647,:712
         // μ′, Σ′ = mean_and_cov(E, pw, 2) (:730-733).  μΣ-AIS: one pass over E yields both (ones row in the MFMA scatter)
         const bool one_pass = pol == MPOPIS_POL_MUSIGMAAISMPPI && wcov_mfma_can_emit_mean(cs);
         // :μΣaismppi on a car env: ws = compute_weights(IT(λ_ais), cost) (:712) is evaluated inside the moments kernel from the costs and the
@@ -98,8 +96,7 @@ int mpopis_handle::ais_update(int n, bool injected) {
         const bool fold = one_pass && weights_in_moments;
         if (!fold) {
             time_begin(3);
-            if (slot_hyper()) launch_weights_slots(d_cost, d_w, B, K, d_sl_nil_ais, d_active, d_status, stream, d_wsum);
-            else launch_weights(d_cost, d_w, B, K, lam, d_active, d_status, stream, d_wsum);
+            launch_weights(d_cost, d_w, B, K, sv_nil_ais(), d_active, d_status, stream, d_wsum);          // λ (:362) / λ_ais (:647,:712)
             if (!one_pass) launch_wmean(d_E, d_w, nullptr, nullptr, d_mu, B, cs, K, 1, d_active, stream);     // μ′ (mean(E, pw, dims=2))
             time_end();
         }
@@ -107,7 +104,7 @@ int mpopis_handle::ais_update(int n, bool injected) {
             time_begin(4);
             launch_wcov_mfma(d_E, d_w, nullptr, K, d_mu, d_Sig, d_part, B, cs, K, ksplit, wcov_sel_batch(), 0.0, 10e-9, d_active, stream, nullptr,
                              one_pass ? d_mu : nullptr, one_pass ? d_Ucur : nullptr, d_wsum,
-                             fold ? d_cost : nullptr, fold ? d_cmin : nullptr, -1 / lam);        // one pass: also pol.U += μ′
+                             fold ? d_cost : nullptr, fold ? d_cmin : nullptr, sv_nil_ais().v);        // one pass: also pol.U += μ′
             time_end();
         }
         if (!one_pass) hipLaunchKernelGGL(k_add_active, dim3((cs + 255) / 256, B), dim3(256), 0, stream, d_mu, d_Ucur, cs, d_active);   // pol.U += μ′
@@ -115,8 +112,7 @@ int mpopis_handle::ais_update(int n, bool injected) {
     }
     if (pol == MPOPIS_POL_PMCMPPI) {                                                          // :802-809
         time_begin(3);
-        if (slot_hyper()) launch_weights_slots(d_cost, d_w, B, K, d_sl_nil_ais, d_active, d_status, stream);
-        else launch_weights(d_cost, d_w, B, K, cfg.lambda_ais, d_active, d_status, stream);
+        launch_weights(d_cost, d_w, B, K, sv_nil_ais(), d_active, d_status, stream);
         time_end();
         time_begin(5);
         launch_alias_build(d_w, d_accept, d_alias, B, K, d_active, stream, d_alias_need, d_alias_stack);                   // Categorical(ws) -> AliasTable
@@ -201,13 +197,13 @@ int mpopis_handle::ais_update(int n, bool injected) {
         time_begin(4);
         const size_t nn = (size_t)cs * cs;
         // Σ^-1 = invcov(MvNormal(Σ′)) of THIS iteration: Σ0^-1 (formed at mpopis_set_Sigma) at n = 1, else from the factor it sampled from
-        const double* S = d_nesS0; size_t Sstride = S0stride;
+        const double* S = S0.nesS; size_t Sstride = S0stride;
         if (n > 1) { launch_nes_potri(d_L, nn, d_tmpS, d_nesS, B, cs, d_active, stream); S = d_nesS; Sstride = nn; }
         // A′: pol.A (shared, or each slot's own) into the first buffer at n = 1, then ping-pong (never in place)
-        const double* Ain = (n == 1) ? d_nesA0 : d_nesA[n & 1];
+        const double* Ain = (n == 1) ? S0.nesA : d_nesA[n & 1];
         double* Aout = d_nesA[(n - 1) & 1];
         launch_nes_update(d_E, d_cost, d_nespart, ksplit, S, Sstride, d_nesM, d_tmpS, d_nesg, d_nesC, Ain, n == 1 ? S0stride : nn, Aout, d_Sig, d_Ucur,
-                          B, cs, K, cfg.cma_sigma, d_active, stream, d_sl_nes_a, d_sl_nes_u);
+                          B, cs, K, sv_nes_a(), sv_nes_u(), d_active, stream);
         time_end();
         return MPOPIS_OK;
     }

@@ -362,9 +362,9 @@ static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle
     int rc = 0;
     rc |= dalloc(h, &h->d_x, (size_t)B * h->ss); rc |= dalloc(h, &h->d_xext, (size_t)B * kMaxCars * kCarExt); rc |= dalloc(h, &h->d_t, B); rc |= dalloc(h, &h->d_done, B);
     rc |= dalloc(h, &h->d_U, (size_t)B * cs); rc |= dalloc(h, &h->d_Ucur, (size_t)B * cs); rc |= dalloc(h, &h->d_Uin, (size_t)B * cs);
-    rc |= dalloc(h, &h->d_Sigma0, nn); rc |= dalloc(h, &h->d_Sig, (size_t)B * nn + kInvsqrtPadDoubles); rc |= dalloc(h, &h->d_L, (size_t)B * nn);
-    rc |= dalloc(h, &h->d_L0, nn); rc |= dalloc(h, &h->d_tmpS, (size_t)B * nn);
-    if (sample_trmm_fusable(cs)) { rc |= dalloc(h, &h->d_L0p, potrf_panel_doubles(cs)); rc |= dalloc(h, &h->d_Lp, (size_t)B * potrf_panel_doubles(cs)); }
+    rc |= dalloc(h, &h->S0sh.Sigma, nn); rc |= dalloc(h, &h->d_Sig, (size_t)B * nn + kInvsqrtPadDoubles); rc |= dalloc(h, &h->d_L, (size_t)B * nn);
+    rc |= dalloc(h, &h->S0sh.L, nn); rc |= dalloc(h, &h->d_tmpS, (size_t)B * nn);
+    if (sample_trmm_fusable(cs)) { rc |= dalloc(h, &h->S0sh.Lp, potrf_panel_doubles(cs)); rc |= dalloc(h, &h->d_Lp, (size_t)B * potrf_panel_doubles(cs)); }
     rc |= dalloc(h, &h->d_coop_flags, potrf_coop_flag_words(B, cs)); rc |= dalloc(h, &h->d_potrf_redo, B); rc |= dalloc(h, &h->d_lan_redo, B); rc |= dalloc(h, &h->d_coop_timeouts, 1);
     rc |= dalloc(h, &h->d_Z, (size_t)B * cs * K); rc |= dalloc(h, &h->d_E, (size_t)B * cs * K);
     rc |= dalloc(h, &h->d_cost, (size_t)B * K); rc |= dalloc(h, &h->d_w, (size_t)B * K);
@@ -393,13 +393,13 @@ static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle
         rc |= dalloc(h, &h->d_fro_part, (size_t)B * ((cs + 15) / 16)); rc |= dalloc(h, &h->d_tri_dinv, trtri_dinv_doubles(B, cs)); rc |= dalloc(h, &h->d_fro, B); rc |= dalloc(h, &h->d_lan_m, B); rc |= dalloc(h, &h->d_lan_prep, lanczos_prep_doubles(B)); rc |= dalloc(h, &h->d_tri_cnt, 2 * (size_t)B);
     }
     if (cfg->policy == MPOPIS_POL_NESMPPI) {
-        rc |= dalloc(h, &h->d_nesA0, nn); rc |= dalloc(h, &h->d_nesS0, nn); rc |= dalloc(h, &h->d_nesS, (size_t)B * nn);
+        rc |= dalloc(h, &h->S0sh.nesA, nn); rc |= dalloc(h, &h->S0sh.nesS, nn); rc |= dalloc(h, &h->d_nesS, (size_t)B * nn);
         rc |= dalloc(h, &h->d_nesA[0], (size_t)B * nn); rc |= dalloc(h, &h->d_nesA[1], (size_t)B * nn); rc |= dalloc(h, &h->d_nesM, (size_t)B * nn);
         rc |= dalloc(h, &h->d_nesg, (size_t)B * cs); rc |= dalloc(h, &h->d_nesC, B); rc |= dalloc(h, &h->d_nespart, nes_scatter_workspace_doubles(B, cs, h->ksplit));
     }
     if (cfg->log_trajectories) rc |= dalloc(h, &h->d_traj, (size_t)B * K * h->T * h->ss);
     if (rc) { g_create_error = h->err; mpopis_destroy(h); return MPOPIS_ERR_HIP; }
-    h->sh_Sigma0 = h->d_Sigma0; h->sh_L0 = h->d_L0; h->sh_L0p = h->d_L0p; h->sh_nesA0 = h->d_nesA0; h->sh_nesS0 = h->d_nesS0;
+    h->S0 = h->S0sh;
     launch_rng_tab_init(h->d_rng_tab, h->stream);
     h->h_status.assign(B, 0);
     if (hipHostMalloc((void**)&h->h_pin, sizeof(double) * B * (h->as + 2)) != hipSuccess) h->h_pin = nullptr;
@@ -588,81 +588,19 @@ int mpopis_get_U(mpopis_handle* h, double* U) {
     return MPOPIS_OK;
 }
 
-// MPPI_Policy_Params Σ handling :66-81 : an as x as cov_mat is block-replicated (block_diagm, utils.jl:9-21);
-// for :mppi the as x as Σ is kept by the reference, which is the same distribution as the
-// block-diagonal cs x cs one used here (Cholesky of a block-diagonal matrix is block-diagonal).
-int mpopis_set_Sigma(mpopis_handle* h, const double* Sigma, int32_t n) {
-    if (!h || !Sigma) return MPOPIS_ERR_ARG;
-    const int cs = h->cs, as = h->as;
-    std::vector<double> full((size_t)cs * cs, 0.0);
-    if (n == cs && h->cfg.policy != MPOPIS_POL_MPPI) {
-        memcpy(full.data(), Sigma, sizeof(double) * cs * cs);
-    } else if (n == as) {
-        for (int t = 0; t < h->T; ++t)
-            for (int j = 0; j < as; ++j)
-                for (int i = 0; i < as; ++i) full[(size_t)(t * as + i) + (size_t)(t * as + j) * cs] = Sigma[i + (size_t)j * as];
-    } else { h->err = "Covariance matrix size problem"; return MPOPIS_ERR_ARG; }     // :79
-    bool diag = true;
-    for (int j = 0; j < cs && diag; ++j) for (int i = 0; i < cs; ++i) if (i != j && full[(size_t)i + (size_t)j * cs] != 0.0) { diag = false; break; }
-    std::vector<double> ds(cs, 0.0);
-    if (diag) for (int i = 0; i < cs; ++i) { const double v = full[(size_t)i + (size_t)i * cs]; if (!(v > 0.0)) { h->err = "PosDefException: Sigma"; return MPOPIS_ERR_NOT_PD; } ds[i] = sqrt(v); }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    // a handle on per-slot Σ (mpopis_set_Sigma_slots) returns to the shared one: the slots' buffers are in use by whatever is still queued, and
-    // d_dscale keeps their values until this call has succeeded
-    const bool was_slots = h->S0stride != 0;
-    if (was_slots) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
-    } else h->sigma_diag = diag;
-    auto bcast_dscale = [&] { hipLaunchKernelGGL(k_bcast_f64, dim3((cs + 255) / 256), dim3(256), 0, h->stream, h->d_dscale0, h->d_dscale, (size_t)cs, h->B); };
-    HIPCHK(h, hipMemcpyAsync(h->sh_Sigma0, full.data(), sizeof(double) * cs * cs, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_dscale0, ds.data(), sizeof(double) * cs, hipMemcpyHostToDevice, h->stream));
-    // per-slot copy for the diagonal-Σ sampler, once per pol.Σ (it used to be re-broadcast by a launch of its own in every AIS iteration)
-    if (!was_slots) bcast_dscale();
-    // factor once: L0 (shared by all slots; the reference refactors the same Σ every call, :307)
-    fill_i32(h->d_status, 0, h->B, h->stream);
-    launch_potrf(h->sh_Sigma0, 0, h->sh_L0, 1, cs, nullptr, h->d_status, nullptr, h->stream, h->potrf_coop(), h->sh_L0p, 0);
-    HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, wait_stream(h->stream));
-    if (h->h_status[0] != 0) { h->err = "PosDefException: Sigma is not positive definite"; return MPOPIS_ERR_NOT_PD; }
-    if (h->cfg.policy == MPOPIS_POL_NESMPPI) {
-        // pol.A = sqrt(pol.Σ) (src/mppi_mpopi_policies.jl:849) and the first iteration's invcov(MvNormal(pol.Σ)) = L0^-T L0^-1, once per pol.Σ.
-        // Diagonal: closed form; otherwise the device's symmetric eigen-solve (d_tmpS / d_nesM are scratch outside a policy step)
-        if (diag) {
-            std::vector<double> a0((size_t)cs * cs, 0.0);
-            for (int i = 0; i < cs; ++i) a0[(size_t)i * (cs + 1)] = ds[i];
-            HIPCHK(h, hipMemcpyAsync(h->sh_nesA0, a0.data(), sizeof(double) * cs * cs, hipMemcpyHostToDevice, h->stream));
-        } else {
-            launch_sym_sqrt(h->sh_Sigma0, h->d_tmpS, h->d_nesM, h->sh_nesA0, h->d_status, cs, h->stream);
-        }
-        launch_nes_potri(h->sh_L0, 0, h->d_tmpS, h->sh_nesS0, 1, cs, nullptr, h->stream);
-        HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, wait_stream(h->stream));
-        HIPCHK(h, hipGetLastError());
-        if (h->h_status[0] != 0) { h->err = "PosDefException: sqrt(Sigma) has a non-positive eigenvalue"; return MPOPIS_ERR_NOT_PD; }
-    }
-    if (was_slots) {
-        h->d_Sigma0 = h->sh_Sigma0; h->d_L0 = h->sh_L0; h->d_L0p = h->sh_L0p; h->d_nesA0 = h->sh_nesA0; h->d_nesS0 = h->sh_nesS0;
-        h->S0stride = 0; h->P0stride = 0; h->sigma_diag = diag;
-        bcast_dscale();
-        HIPCHK(h, wait_stream(h->stream));
-    }
-    return MPOPIS_OK;
-}
-
-// pol.Σ per slot.  Everything is formed in buffers that are scratch outside a policy step (d_tmpS: the B matrices; d_L / d_Lp: their factors and
-// panels; :nesmppi d_nesA[0] / d_nesA[1]: sqrt(Σ_b) and Σ_b^-1, with d_nesM / d_nesS under them) and copied into the slots' own buffers only when every
-// slot has passed, so a refused call leaves the handle as it was.
-int mpopis_set_Sigma_slots(mpopis_handle* h, const double* Sigma, int32_t n) {
-    if (!h || !Sigma) { if (h) h->err = "mpopis_set_Sigma_slots: null argument"; return MPOPIS_ERR_ARG; }
-    const int cs = h->cs, as = h->as, B = h->B_full;
+// One routine sets pol.Σ, shared (one matrix for every slot, stride 0) or per slot (B matrices).  Everything is formed in buffers that are scratch
+// outside a policy step (d_tmpS: the matrices; d_L / d_Lp: their factors and panels; :nesmppi d_nesA[0] / d_nesA[1]: sqrt(Σ) and Σ^-1, with d_nesM /
+// d_nesS under them) and copied into the destination set only when every matrix has passed, so a refused call leaves the handle as it was.
+static int set_Sigma0(mpopis_handle* h, const double* Sigma, int32_t n, bool per_slot) {
+    const int cs = h->cs, as = h->as, B = h->B_full, M = per_slot ? B : 1;
     const size_t nn = (size_t)cs * cs, pd = sample_trmm_fusable(cs) ? potrf_panel_doubles(cs) : 0;
     const bool nes = h->cfg.policy == MPOPIS_POL_NESMPPI;
+    auto of_slot = [per_slot](int b) { return per_slot ? " of slot " + std::to_string(b) : std::string(); };
     if (!((n == cs && h->cfg.policy != MPOPIS_POL_MPPI) || n == as)) { h->err = "Covariance matrix size problem"; return MPOPIS_ERR_ARG; }     // :79
-    std::vector<double> full((size_t)B * nn, 0.0), ds((size_t)B * cs, 0.0);
-    std::vector<char> slot_diag(B, 1);
+    std::vector<double> full((size_t)M * nn, 0.0), ds((size_t)M * cs, 0.0);
+    std::vector<char> slot_diag(M, 1);
     bool diag = true;
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < M; ++b) {
         const double* Sb = Sigma + (size_t)b * n * n;
         double* fb = full.data() + (size_t)b * nn;
         if (n == cs && h->cfg.policy != MPOPIS_POL_MPPI) memcpy(fb, Sb, sizeof(double) * nn);
@@ -674,15 +612,16 @@ int mpopis_set_Sigma_slots(mpopis_handle* h, const double* Sigma, int32_t n) {
         if (slot_diag[b])
             for (int i = 0; i < cs; ++i) {
                 const double v = fb[(size_t)i * (cs + 1)];
-                if (!(v > 0.0)) { h->err = "PosDefException: Sigma of slot " + std::to_string(b); return MPOPIS_ERR_NOT_PD; }
+                if (!(v > 0.0)) { h->err = "PosDefException: Sigma" + of_slot(b); return MPOPIS_ERR_NOT_PD; }
                 ds[(size_t)b * cs + i] = sqrt(v);
             }
         else diag = false;
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (the set in force and the scratch are in use by whatever is still queued)
     for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
-    if (!h->sl_Sigma0) {                                        // first use: the slots' own buffers
+    mpopis_handle::Sigma0Set& dst = per_slot ? h->S0sl : h->S0sh;
+    if (!dst.Sigma) {                                           // first use of per-slot Σ: the slots' own buffers
         double* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
         const size_t want[5] = {(size_t)B * nn, (size_t)B * nn, (size_t)B * pd, nes ? (size_t)B * nn : 0, nes ? (size_t)B * nn : 0};
         for (int i = 0; i < 5; ++i)
@@ -693,15 +632,26 @@ int mpopis_set_Sigma_slots(mpopis_handle* h, const double* Sigma, int32_t n) {
                 return MPOPIS_ERR_HIP;
             }
         for (double* q : p) if (q) h->allocs.push_back(q);
-        h->sl_Sigma0 = p[0]; h->sl_L0 = p[1]; h->sl_L0p = p[2]; h->sl_nesA0 = p[3]; h->sl_nesS0 = p[4];
+        dst = {p[0], p[1], p[2], p[3], p[4]};
     }
-    HIPCHK(h, hipMemcpyAsync(h->d_tmpS, full.data(), sizeof(double) * B * nn, hipMemcpyHostToDevice, h->stream));
+    auto read_status = [&]() -> int {
+        HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int) * M, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipGetLastError());
+        return MPOPIS_OK;
+    };
+    // factor once (the reference refactors the same Σ every call, :307)
+    HIPCHK(h, hipMemcpyAsync(h->d_tmpS, full.data(), sizeof(double) * M * nn, hipMemcpyHostToDevice, h->stream));
     fill_i32(h->d_status, 0, B, h->stream);
-    launch_potrf(h->d_tmpS, nn, h->d_L, B, cs, nullptr, h->d_status, nullptr, h->stream, h->potrf_coop(), pd ? h->d_Lp : nullptr, pd);
+    launch_potrf(h->d_tmpS, nn, h->d_L, M, cs, nullptr, h->d_status, nullptr, h->stream, h->potrf_coop(), pd ? h->d_Lp : nullptr, pd);
+    if (int rc = read_status()) return rc;
+    for (int b = 0; b < M; ++b)
+        if (h->h_status[b] != 0) { h->err = "PosDefException: Sigma" + of_slot(b) + " is not positive definite"; return MPOPIS_ERR_NOT_PD; }
     if (nes) {
-        // pol.A = sqrt(pol.Σ) and invcov(MvNormal(pol.Σ)) per slot, by the rule of mpopis_set_Sigma: closed form for a diagonal slot, else the eigen-solve
+        // pol.A = sqrt(pol.Σ) (src/mppi_mpopi_policies.jl:849) and the first iteration's invcov(MvNormal(pol.Σ)) = L0^-T L0^-1, once per pol.Σ.
+        // A diagonal matrix: closed form; otherwise the device's symmetric eigen-solve
         std::vector<double> a0(nn);
-        for (int b = 0; b < B; ++b) {
+        for (int b = 0; b < M; ++b) {
             if (slot_diag[b]) {
                 std::fill(a0.begin(), a0.end(), 0.0);
                 for (int i = 0; i < cs; ++i) a0[(size_t)i * (cs + 1)] = ds[(size_t)b * cs + i];
@@ -711,24 +661,38 @@ int mpopis_set_Sigma_slots(mpopis_handle* h, const double* Sigma, int32_t n) {
             }
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));             // (d_nesM is the eigen-solves' workspace until here)
-        launch_nes_potri(h->d_L, nn, h->d_nesM, h->d_nesA[1], B, cs, nullptr, h->stream);
+        launch_nes_potri(h->d_L, nn, h->d_nesM, h->d_nesA[1], M, cs, nullptr, h->stream);
+        if (int rc = read_status()) return rc;
+        for (int b = 0; b < M; ++b)
+            if (h->h_status[b] != 0) {
+                h->err = per_slot ? "PosDefException: Sigma" + of_slot(b) + " is not positive definite" : "PosDefException: sqrt(Sigma) has a non-positive eigenvalue";
+                return MPOPIS_ERR_NOT_PD;
+            }
     }
-    HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    copy_f64(h->d_tmpS, dst.Sigma, (size_t)M * nn, h->stream);
+    copy_f64(h->d_L, dst.L, (size_t)M * nn, h->stream);
+    if (pd) copy_f64(h->d_Lp, dst.Lp, (size_t)M * pd, h->stream);
+    if (nes) { copy_f64(h->d_nesA[0], dst.nesA, (size_t)M * nn, h->stream); copy_f64(h->d_nesA[1], dst.nesS, (size_t)M * nn, h->stream); }
+    // sqrt(diag) per slot for the diagonal-Σ sampler, once per pol.Σ
+    HIPCHK(h, hipMemcpyAsync(per_slot ? h->d_dscale : h->d_dscale0, ds.data(), sizeof(double) * M * cs, hipMemcpyHostToDevice, h->stream));
+    if (!per_slot) hipLaunchKernelGGL(k_bcast_f64, dim3((cs + 255) / 256), dim3(256), 0, h->stream, h->d_dscale0, h->d_dscale, (size_t)cs, B);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
-    for (int b = 0; b < B; ++b)
-        if (h->h_status[b] != 0) { h->err = "PosDefException: Sigma of slot " + std::to_string(b) + " is not positive definite"; return MPOPIS_ERR_NOT_PD; }
-    copy_f64(h->d_tmpS, h->sl_Sigma0, (size_t)B * nn, h->stream);
-    copy_f64(h->d_L, h->sl_L0, (size_t)B * nn, h->stream);
-    if (pd) copy_f64(h->d_Lp, h->sl_L0p, (size_t)B * pd, h->stream);
-    if (nes) { copy_f64(h->d_nesA[0], h->sl_nesA0, (size_t)B * nn, h->stream); copy_f64(h->d_nesA[1], h->sl_nesS0, (size_t)B * nn, h->stream); }
-    HIPCHK(h, hipMemcpyAsync(h->d_dscale, ds.data(), sizeof(double) * B * cs, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipGetLastError());
-    h->d_Sigma0 = h->sl_Sigma0; h->d_L0 = h->sl_L0; h->d_L0p = h->sl_L0p;
-    if (nes) { h->d_nesA0 = h->sl_nesA0; h->d_nesS0 = h->sl_nesS0; }
-    h->S0stride = nn; h->P0stride = pd; h->sigma_diag = diag;
+    h->S0 = dst;
+    h->S0stride = per_slot ? nn : 0; h->P0stride = per_slot ? pd : 0; h->sigma_diag = diag;
     return MPOPIS_OK;
+}
+
+// MPPI_Policy_Params Σ handling :66-81 : an as x as cov_mat is block-replicated (block_diagm, utils.jl:9-21);
+// for :mppi the as x as Σ is kept by the reference, which is the same distribution as the
+// block-diagonal cs x cs one used here (Cholesky of a block-diagonal matrix is block-diagonal).
+int mpopis_set_Sigma(mpopis_handle* h, const double* Sigma, int32_t n) {
+    if (!h || !Sigma) return MPOPIS_ERR_ARG;
+    return set_Sigma0(h, Sigma, n, false);
+}
+int mpopis_set_Sigma_slots(mpopis_handle* h, const double* Sigma, int32_t n) {
+    if (!h || !Sigma) { if (h) h->err = "mpopis_set_Sigma_slots: null argument"; return MPOPIS_ERR_ARG; }
+    return set_Sigma0(h, Sigma, n, true);
 }
 
 // λ, α, λ_ais, σ per slot.  A setup call (it waits for everything queued); the kernels read what is formed here on the host.
@@ -819,7 +783,7 @@ int mpopis_get_Sigma(mpopis_handle* h, double* out) {
     // d_tmpS is scratch outside a policy step
     const double* scale = (pol == MPOPIS_POL_CMAMPPI && h->N > 1) ? h->d_sig2 : nullptr;     // MvNormal(σ²Σ′) :550-554
     hipLaunchKernelGGL(k_scaled_copy_f64, dim3((nn + 255) / 256, h->B), dim3(256), 0, h->stream,
-                       sigma_fixed ? h->d_Sigma0 : h->d_Sig, sigma_fixed ? h->S0stride : nn, scale, h->d_tmpS, nn);
+                       sigma_fixed ? h->S0.Sigma : h->d_Sig, sigma_fixed ? h->S0stride : nn, scale, h->d_tmpS, nn);
     HIPCHK(h, hipMemcpyAsync(out, h->d_tmpS, sizeof(double) * h->B * nn, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, wait_stream(h->stream));
     return MPOPIS_OK;
@@ -840,8 +804,7 @@ int mpopis_rollout_costs(mpopis_handle* h, const double* x0, const double* U, co
     const double* gv = nullptr;
     if (h->use_gvec()) {
         HIPCHK(h, hipMemcpyAsync(h->d_tmpS, Sigma_inv, sizeof(double) * cs * cs, hipMemcpyHostToDevice, h->stream));
-        if (h->slot_hyper()) launch_gvec_from_inv_slots(h->d_tmpS, h->d_Uin, h->d_sl_gamma, h->d_gvec, B, cs, h->stream);
-        else launch_gvec_from_inv(h->d_tmpS, h->d_Uin, h->gamma, h->d_gvec, B, cs, h->stream);
+        launch_gvec_from_inv(h->d_tmpS, h->d_Uin, h->sv_gamma(), h->d_gvec, B, cs, h->stream);
         gv = h->d_gvec;
     }
     fill_i32(h->d_status, 0, B, h->stream);
@@ -1135,7 +1098,7 @@ void mpopis_handle::shift_slots(ptrdiff_t db) {
     mv(d_coop_flags, (ptrdiff_t)potrf_coop_flag_words(1, cs)); mv(d_potrf_redo, 1); mv(d_lan_redo, 1);
     mv(d_nesS, nn); mv(d_nesA[0], nn); mv(d_nesA[1], nn); mv(d_nesM, nn); mv(d_nesg, cs); mv(d_nesC, 1); mv(d_nespart, (ptrdiff_t)nes_scatter_workspace_doubles(1, cs, ksplit));
     mv(alive_gate, 1); mv(d_hs, kHarnessDoubles); mv(d_alive, 1); mv(d_actlog, actlog_stride);
-    mv(d_Sigma0, (ptrdiff_t)S0stride); mv(d_L0, (ptrdiff_t)S0stride); mv(d_L0p, (ptrdiff_t)P0stride); mv(d_nesA0, (ptrdiff_t)S0stride); mv(d_nesS0, (ptrdiff_t)S0stride);   // per-slot pol.Σ (stride 0: shared)
+    mv(S0.Sigma, (ptrdiff_t)S0stride); mv(S0.L, (ptrdiff_t)S0stride); mv(S0.Lp, (ptrdiff_t)P0stride); mv(S0.nesA, (ptrdiff_t)S0stride); mv(S0.nesS, (ptrdiff_t)S0stride);   // per-slot pol.Σ (stride 0: shared)
     mv(d_sl_nil, 1); mv(d_sl_nil_ais, 1); mv(d_sl_gamma, 1); mv(d_sl_sigma, 1); mv(d_sl_nes_a, 1); mv(d_sl_nes_u, 1);          // per-slot λ, α, λ_ais, σ (null: the scalars)
     mv(custom.table_view, (ptrdiff_t)custom.table_stride);                     // a custom env's per-slot tables (stride 0: one shared table)
 }
@@ -1313,8 +1276,8 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
     launch_step_begin(status_sticky ? nullptr : d_status, d_active, alive_gate, d_iters, d_U, d_Uin, d_Ucur, B, cs,
                       env.kind == MPOPIS_ENV_CAR ? d_x : nullptr, d_xext, env.ncars, stream, weights_in_moments ? d_cmin : nullptr, env.track, d_iters_acc);
     if (!sigma_fixed) {                                                                                                          // Σ′ = pol.Σ
-        if (S0stride) copy_f64(d_Sigma0, d_Sig, (size_t)B * nn, stream);                                                          // (each slot's own)
-        else hipLaunchKernelGGL(k_bcast_f64, dim3((nn + 255) / 256), dim3(256), 0, stream, d_Sigma0, d_Sig, nn, B);
+        if (S0stride) copy_f64(S0.Sigma, d_Sig, (size_t)B * nn, stream);                                                         // (each slot's own)
+        else hipLaunchKernelGGL(k_bcast_f64, dim3((nn + 255) / 256), dim3(256), 0, stream, S0.Sigma, d_Sig, nn, B);
     }
     if (pol == MPOPIS_POL_CMAMPPI) cma_begin();
     // Shapes the fused sampler does not cover (cs > 128: Z goes through memory anyway) with device RNG, a dense proposal from iteration 2 on
@@ -1339,7 +1302,7 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
         const bool cma_scaled = pol == MPOPIS_POL_CMAMPPI && N > 1;
         const double* osc2 = (cma_scaled && n == 1) ? cma_sigma2() : nullptr;
         const bool own_factor = !(sigma_fixed || n == 1);      // this iteration factors its own Σ′ (else: the factor of pol.Σ, shared or per slot)
-        if (!own_factor) { Lp = d_L0; Lstride = S0stride; }
+        if (!own_factor) { Lp = S0.L; Lstride = S0stride; }
         else {
             time_begin(2);
             launch_potrf(d_Sig, nn, d_L, B, cs, cma_scaled ? cma_sigma2() : nullptr, d_status, d_active, stream, potrf_coop(), d_Lp, potrf_panel_doubles(cs));
@@ -1347,10 +1310,7 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
             Lp = d_L; Lstride = nn;
         }
         cur_L = Lp; cur_Lstride = Lstride; cur_L_scaled = cma_scaled && n > 1;
-        if (use_gvec()) {
-            if (slot_hyper()) launch_chol_solve_gvec_slots(Lp, Lstride, d_Uin, d_sl_gamma, d_gvec, B, cs, d_active, stream, osc2);
-            else launch_chol_solve_gvec(Lp, Lstride, d_Uin, gamma, d_gvec, B, cs, d_active, stream, osc2);
-        }
+        if (use_gvec()) launch_chol_solve_gvec(Lp, Lstride, d_Uin, sv_gamma(), d_gvec, B, cs, d_active, stream, osc2);
         // ---- E = rand(rng, P, K) ----------------------------------------------------------------
         time_begin(1);
         if (first_diag && !(pol == MPOPIS_POL_CMAMPPI)) dsc = d_dscale;        // sqrt(diag Σ) per slot, written by mpopis_set_Sigma
@@ -1369,7 +1329,7 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
         } else if (!dsc && pol != MPOPIS_POL_MPPI) {
             // dense proposal: draw inside the unwhitening kernel when the shape allows it (no Z round trip through HBM)
             fused = launch_sample_trmm_fused(Lp, Lstride, d_E, B, cs, K, d_seeds, (uint32_t)mpc_step, (uint32_t)(n - 1), d_active, stream, d_rng_tab,
-                                             own_factor ? d_Lp : d_L0p, own_factor ? potrf_panel_doubles(cs) : P0stride, osc2);
+                                             own_factor ? d_Lp : S0.Lp, own_factor ? potrf_panel_doubles(cs) : P0stride, osc2);
             if (!fused) launch_sample_normal(Zdst, B, cs, K, as, 0, d_seeds, (uint32_t)mpc_step, (uint32_t)(n - 1), dsc, d_active, stream, d_rng_tab);
         } else {
             launch_sample_normal(Zdst, B, cs, K, as, pol == MPOPIS_POL_MPPI, d_seeds, (uint32_t)mpc_step, (uint32_t)(n - 1), dsc, d_active, stream, d_rng_tab);
@@ -1416,8 +1376,7 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
     }
     // weights = compute_weights(IT(λ), cost); weighted_noise = Σ_k w_k (E_k + (pol.U - U_orig)); roll
     time_begin(3);
-    if (slot_hyper()) launch_weights_slots(d_cost, d_w, B, K, d_sl_nil, alive_gate, d_status, stream);
-    else launch_weights(d_cost, d_w, B, K, cfg.lambda, alive_gate, d_status, stream);
+    launch_weights(d_cost, d_w, B, K, sv_nil(), alive_gate, d_status, stream);
     launch_wmean(d_E, d_w, d_Ucur, d_Uin, d_wn, B, cs, K, 0, alive_gate, stream);
     launch_finalize_env(d_wn, d_U, d_control, B, cs, as, T, env, stream);
     time_end();

@@ -31,16 +31,16 @@ struct mpopis_handle {
     double *d_x = nullptr, *d_xext = nullptr, *d_U = nullptr, *d_Ucur = nullptr, *d_Uin = nullptr;
     int *d_t = nullptr, *d_done = nullptr;
     // proposal
-    double *d_Sigma0 = nullptr, *d_L0 = nullptr, *d_dscale0 = nullptr;   // shared pol.Σ, its factor, sqrt(diag)
+    double* d_dscale0 = nullptr;                  // sqrt(diag) of the shared pol.Σ
     double *d_Sig = nullptr, *d_L = nullptr, *d_tmpS = nullptr, *d_dscale = nullptr;
-    double *d_L0p = nullptr, *d_Lp = nullptr;     // the factors once more in the fused sampler's staging layout (potrf_panel_doubles(cs) per matrix; cs <= 128)
+    double* d_Lp = nullptr;                       // the factors once more in the fused sampler's staging layout (potrf_panel_doubles(cs) per matrix; cs <= 128)
     bool sigma_diag = false;                      // pol.Σ diagonal (per-slot Σ: in every slot); d_dscale then holds each slot's sqrt(diag)
-    // Per-slot pol.Σ (mpopis_set_Sigma_slots).  d_Sigma0 / d_L0 / d_L0p / d_nesA0 / d_nesS0 above are what is IN FORCE: the shared buffers
-    // (sh_*, stride 0) until the first call, then the [B] copies (sl_*, allocated by that call; strides cs² and the panel size), moved with the
-    // slot views.  mpopis_set_Sigma points them back at the shared buffers.
+    // pol.Σ, its factor, the factor's sampler panel and, for :nesmppi, A0 = sqrt(pol.Σ) and Σ0^-1.  S0 is the set IN FORCE: the shared buffers
+    // (S0sh, stride 0) until the first mpopis_set_Sigma_slots, then the [B] copies (S0sl, allocated by that call; strides cs² and the panel size),
+    // moved with the slot views.  mpopis_set_Sigma switches back to the shared set.
+    struct Sigma0Set { double *Sigma = nullptr, *L = nullptr, *Lp = nullptr, *nesA = nullptr, *nesS = nullptr; };
+    Sigma0Set S0, S0sh, S0sl;
     size_t S0stride = 0, P0stride = 0;
-    double *sh_Sigma0 = nullptr, *sh_L0 = nullptr, *sh_L0p = nullptr, *sh_nesA0 = nullptr, *sh_nesS0 = nullptr;
-    double *sl_Sigma0 = nullptr, *sl_L0 = nullptr, *sl_L0p = nullptr, *sl_nesA0 = nullptr, *sl_nesS0 = nullptr;
     // Per-slot λ, α, λ_ais, σ (mpopis_set_slot_hyper).  sl_host: the four arrays in force ([4][B], empty = the config's scalars in every slot);
     // the device arrays hold what the kernels consume, formed on the host like the scalars they replace: -1/λ_b, -1/λ_ais,b (-1/λ_b under :imppi),
     // γ_b, σ_b, and for :nesmppi -sf_b/K² and sf_b/K.  Null while the handle runs on the scalars; moved with the slot views.
@@ -50,6 +50,13 @@ struct mpopis_handle {
     bool sl_any_gamma = false;
     bool slot_hyper() const { return d_sl_nil != nullptr; }
     bool use_gvec() const { return slot_hyper() ? sl_any_gamma : gamma != 0.0; }      // γ U' Σ^-1 E enters the cost in some slot
+    // what the launchers consume: the config's scalar paired with the per-slot array of the same meaning (null: the scalar in every slot)
+    mpopis::SlotVal sv_nil() const { return {-1 / cfg.lambda, d_sl_nil}; }
+    mpopis::SlotVal sv_nil_ais() const { return {-1 / (cfg.policy == MPOPIS_POL_IMPPI ? cfg.lambda : cfg.lambda_ais), d_sl_nil_ais}; }      // :362 / :647,:712
+    mpopis::SlotVal sv_gamma() const { return {gamma, d_sl_gamma}; }
+    mpopis::SlotVal sv_sigma() const { return {cfg.cma_sigma, d_sl_sigma}; }
+    mpopis::SlotVal sv_nes_a() const { return {-cfg.cma_sigma / ((double)K * K), d_sl_nes_a}; }
+    mpopis::SlotVal sv_nes_u() const { return {cfg.cma_sigma / K, d_sl_nes_u}; }
     bool fold_weights_cfg = false;                // what weights_in_moments is while λ_ais is the config's scalar
     // samples / costs / weights
     double *d_Z = nullptr, *d_E = nullptr, *d_Zin = nullptr, *d_cost = nullptr, *d_w = nullptr;
@@ -84,8 +91,8 @@ struct mpopis_handle {
     int* d_alias_need = nullptr;                                                           // :pmcmppi: slots whose alias table the parallel construction could not certify
     int* d_lan_m = nullptr;                                                                // Lanczos steps taken per slot (diagnostic)
     unsigned long long* d_tri_cnt = nullptr;                                               // [B][2]: arrival counter of a slot's trace workgroups (the last one prepares the Lanczos run) and their ||Σ||_inf; zero between launches
-    // :nesmppi: A0 = sqrt(pol.Σ) and Σ0^-1 (shared, formed at mpopis_set_Sigma); per slot Σ^-1 of the iteration, A′ (ping-pong), M / G, the scatter's g, C, partials
-    double *d_nesA0 = nullptr, *d_nesS0 = nullptr, *d_nesS = nullptr, *d_nesA[2] = {nullptr, nullptr}, *d_nesM = nullptr, *d_nesg = nullptr, *d_nesC = nullptr, *d_nespart = nullptr;
+    // :nesmppi (A0 = sqrt(pol.Σ) and Σ0^-1 live in S0): per slot Σ^-1 of the iteration, A′ (ping-pong), M / G, the scatter's g, C, partials
+    double *d_nesS = nullptr, *d_nesA[2] = {nullptr, nullptr}, *d_nesM = nullptr, *d_nesg = nullptr, *d_nesC = nullptr, *d_nespart = nullptr;
     double *d_qdist = nullptr, *d_qbeta = nullptr; int* d_qwithin = nullptr;
     // Level-3 harness
     double* d_hs = nullptr; int* d_alive = nullptr; const int* alive_gate = nullptr; bool status_sticky = false;

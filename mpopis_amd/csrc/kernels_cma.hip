@@ -13,17 +13,13 @@ namespace mpopis {
 // vectors (d_cma_vec[b][3*cs]): pσ | pΣ | δw.   sig2[b] = σ² (scale of the next proposal, :551).
 struct CmaConsts { double mu_eff, c_sigma, d_sigma, c_Sigma, c1, c_mu, E_cma; int m_elite; };
 
-__global__ void __launch_bounds__(256) k_cma_begin(double* scal, double* vec, double* sig2, double sigma0, int cs, int B) {
+// Sig = const double*: per-slot σ₀ (mpopis_set_slot_hyper)
+template <class Sig>
+__global__ void __launch_bounds__(256) k_cma_begin(double* scal, double* vec, double* sig2, Sig sigma0_arg, int cs, int B) {
     const int b = blockIdx.x;
+    const double sigma0 = slot_val(sigma0_arg, b);
     for (int i = threadIdx.x; i < 3 * cs; i += 256) vec[(size_t)b * 3 * cs + i] = 0.0;        // pσ, pΣ = 0 (:545)
     if (threadIdx.x == 0) { scal[b * 8 + 0] = sigma0; sig2[b] = sigma0 * sigma0; }              // σ = pol.σ (:536)
-}
-
-// per-slot σ₀ (mpopis_set_slot_hyper)
-__global__ void __launch_bounds__(256) k_cma_begin_slots(double* scal, double* vec, double* sig2, const double* __restrict__ sigma0, int cs, int B) {
-    const int b = blockIdx.x;
-    for (int i = threadIdx.x; i < 3 * cs; i += 256) vec[(size_t)b * 3 * cs + i] = 0.0;
-    if (threadIdx.x == 0) { const double s0 = sigma0[b]; scal[b * 8 + 0] = s0; sig2[b] = s0 * s0; }
 }
 
 // δw given (gather_mean with cw); this kernel: pol.U += σ δw; pσ; σ; hσ; pΣ; temp_sum
@@ -116,11 +112,9 @@ __global__ void __launch_bounds__(256) k_cma_sigma_update(double* Sig, const dou
     S[j + (size_t)i * cs] = v;
 }
 
-void launch_cma_begin(double* scal, double* vec, double* sig2, double sigma0, int cs, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_cma_begin, dim3(B), dim3(256), 0, s, scal, vec, sig2, sigma0, cs, B);
-}
-void launch_cma_begin_slots(double* scal, double* vec, double* sig2, const double* sigma0, int cs, int B, hipStream_t s) {
-    hipLaunchKernelGGL(k_cma_begin_slots, dim3(B), dim3(256), 0, s, scal, vec, sig2, sigma0, cs, B);
+void launch_cma_begin(double* scal, double* vec, double* sig2, SlotVal sigma0, int cs, int B, hipStream_t s) {
+    if (sigma0.per_slot) hipLaunchKernelGGL(k_cma_begin<const double*>, dim3(B), dim3(256), 0, s, scal, vec, sig2, sigma0.per_slot, cs, B);
+    else hipLaunchKernelGGL(k_cma_begin<double>, dim3(B), dim3(256), 0, s, scal, vec, sig2, sigma0.v, cs, B);
 }
 void launch_cma_paths(const double* Cdw, const double* fro, const double* E, const int32_t* order, const double* ws, double* Ucur, double* scal, double* vec,
                       double* sig2, int B, int cs, int K, int n_iter, const double* consts7, int m_elite, const int* active, hipStream_t s) {

@@ -776,13 +776,15 @@ void launch_potrf(const double* A, size_t Astride, double* L, int B, int n, cons
 
 // g = Σ⁻¹ (γ U_orig) through the Cholesky factor (Σ symmetric => row vector γ U_orig' Σ⁻¹ = g').
 // Slow path: only taken when α != 1 (γ != 0); no BASELINE config uses it.
-// k_chol_solve_gvec_slots below is a copy of this body that reads γ per slot: a fix here belongs there too.
+// Gam = const double*: per-slot γ_b = λ_b (1 - α_b) (mpopis_set_slot_hyper); a slot with γ_b = 0 gets a zero row.
+template <class Gam>
 __global__ void __launch_bounds__(256) k_chol_solve_gvec(const double* __restrict__ L, size_t Lstride, const double* __restrict__ Uorig,
-                                                         double gamma, double* __restrict__ g, int n, const int* active, const double* inv_scale2) {
+                                                         Gam gamma_arg, double* __restrict__ g, int n, const int* active, const double* inv_scale2) {
     MPOPIS_HI_PRIO();
     extern __shared__ __attribute__((aligned(16))) double y[];
     const int b = blockIdx.x;
     if (active && !active[b]) return;
+    const double gamma = slot_val(gamma_arg, b);
     const double* Lb = L + (size_t)b * Lstride;
     for (int i = threadIdx.x; i < n; i += 256) y[i] = gamma * Uorig[(size_t)b * n + i];
     __syncthreads();
@@ -803,69 +805,27 @@ __global__ void __launch_bounds__(256) k_chol_solve_gvec(const double* __restric
     const double isc = inv_scale2 ? 1.0 / inv_scale2[b] : 1.0;
     for (int i = threadIdx.x; i < n; i += 256) g[(size_t)b * n + i] = inv_scale2 ? y[i] * isc : y[i];
 }
-// per-slot γ_b = λ_b (1 - α_b) (mpopis_set_slot_hyper); a slot with γ_b = 0 gets a zero row.  (A copy for the same reason as k_weights_slots.)
-__global__ void __launch_bounds__(256) k_chol_solve_gvec_slots(const double* __restrict__ L, size_t Lstride, const double* __restrict__ Uorig,
-                                                         const double* __restrict__ gamma_b, double* __restrict__ g, int n, const int* active, const double* inv_scale2) {
-    MPOPIS_HI_PRIO();
-    extern __shared__ __attribute__((aligned(16))) double y[];
-    const int b = blockIdx.x;
-    if (active && !active[b]) return;
-    const double* Lb = L + (size_t)b * Lstride;
-    const double gamma = gamma_b[b];
-    for (int i = threadIdx.x; i < n; i += 256) y[i] = gamma * Uorig[(size_t)b * n + i];
-    __syncthreads();
-    for (int j = 0; j < n; ++j) {                     // forward: L y = γU
-        if (threadIdx.x == 0) y[j] = y[j] / Lb[(size_t)j + (size_t)j * n];
-        __syncthreads();
-        const double yj = y[j];
-        for (int i = j + 1 + threadIdx.x; i < n; i += 256) y[i] = fma(-Lb[(size_t)i + (size_t)j * n], yj, y[i]);
-        __syncthreads();
-    }
-    for (int j = n - 1; j >= 0; --j) {                // backward: L' g = y
-        if (threadIdx.x == 0) y[j] = y[j] / Lb[(size_t)j + (size_t)j * n];
-        __syncthreads();
-        const double yj = y[j];
-        for (int i = threadIdx.x; i < j; i += 256) y[i] = fma(-Lb[(size_t)j + (size_t)i * n], yj, y[i]);
-        __syncthreads();
-    }
-    const double isc = inv_scale2 ? 1.0 / inv_scale2[b] : 1.0;
-    for (int i = threadIdx.x; i < n; i += 256) g[(size_t)b * n + i] = inv_scale2 ? y[i] * isc : y[i];
-}
-void launch_chol_solve_gvec_slots(const double* L, size_t Lstride, const double* Uorig, const double* gamma, double* g, int B, int n, const int* active, hipStream_t s,
-                                  const double* inv_scale2) {
-    hipLaunchKernelGGL(k_chol_solve_gvec_slots, dim3(B), dim3(256), n * sizeof(double), s, L, Lstride, Uorig, gamma, g, n, active, inv_scale2);
-}
-void launch_chol_solve_gvec(const double* L, size_t Lstride, const double* Uorig, double gamma, double* g, int B, int n, const int* active, hipStream_t s,
+void launch_chol_solve_gvec(const double* L, size_t Lstride, const double* Uorig, SlotVal gamma, double* g, int B, int n, const int* active, hipStream_t s,
                             const double* inv_scale2) {
-    hipLaunchKernelGGL(k_chol_solve_gvec, dim3(B), dim3(256), n * sizeof(double), s, L, Lstride, Uorig, gamma, g, n, active, inv_scale2);
+    if (gamma.per_slot) hipLaunchKernelGGL(k_chol_solve_gvec<const double*>, dim3(B), dim3(256), n * sizeof(double), s, L, Lstride, Uorig, gamma.per_slot, g, n, active, inv_scale2);
+    else hipLaunchKernelGGL(k_chol_solve_gvec<double>, dim3(B), dim3(256), n * sizeof(double), s, L, Lstride, Uorig, gamma.v, g, n, active, inv_scale2);
 }
 
-// Level-1 entry: caller supplies Σ_inv; g[j] = Σ_i (γ U_orig[i]) Σ_inv[i][j]   (:272)
-__global__ void __launch_bounds__(256) k_gvec_from_inv(const double* __restrict__ Sinv, const double* __restrict__ Uorig, double gamma,
+// Level-1 entry: caller supplies Σ_inv; g[j] = Σ_i (γ U_orig[i]) Σ_inv[i][j]   (:272); γ or per-slot γ_b on the one Σ_inv of the call
+template <class Gam>
+__global__ void __launch_bounds__(256) k_gvec_from_inv(const double* __restrict__ Sinv, const double* __restrict__ Uorig, Gam gamma_arg,
                                                        double* __restrict__ g, int n) {
     const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
+    const double gamma = slot_val(gamma_arg, b);
     double v = 0.0;
     for (int i = 0; i < n; ++i) v = fma(gamma * Uorig[(size_t)b * n + i], Sinv[(size_t)i + (size_t)j * n], v);
     g[(size_t)b * n + j] = v;
 }
-void launch_gvec_from_inv(const double* Sinv, const double* Uorig, double gamma, double* g, int B, int n, hipStream_t s) {
-    hipLaunchKernelGGL(k_gvec_from_inv, dim3((n + 255) / 256, B), dim3(256), 0, s, Sinv, Uorig, gamma, g, n);
+void launch_gvec_from_inv(const double* Sinv, const double* Uorig, SlotVal gamma, double* g, int B, int n, hipStream_t s) {
+    if (gamma.per_slot) hipLaunchKernelGGL(k_gvec_from_inv<const double*>, dim3((n + 255) / 256, B), dim3(256), 0, s, Sinv, Uorig, gamma.per_slot, g, n);
+    else hipLaunchKernelGGL(k_gvec_from_inv<double>, dim3((n + 255) / 256, B), dim3(256), 0, s, Sinv, Uorig, gamma.v, g, n);
 }
-// per-slot γ_b on the one Σ_inv of the call
-__global__ void __launch_bounds__(256) k_gvec_from_inv_slots(const double* __restrict__ Sinv, const double* __restrict__ Uorig, const double* __restrict__ gamma,
-                                                             double* __restrict__ g, int n) {
-    const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    const double gm = gamma[b];
-    double v = 0.0;
-    for (int i = 0; i < n; ++i) v = fma(gm * Uorig[(size_t)b * n + i], Sinv[(size_t)i + (size_t)j * n], v);
-    g[(size_t)b * n + j] = v;
-}
-void launch_gvec_from_inv_slots(const double* Sinv, const double* Uorig, const double* gamma, double* g, int B, int n, hipStream_t s) {
-    hipLaunchKernelGGL(k_gvec_from_inv_slots, dim3((n + 255) / 256, B), dim3(256), 0, s, Sinv, Uorig, gamma, g, n);
-}
-
 // mean over gathered columns: mu[r] = (1/m) Σ_j X[r][idx[j]] ; optionally weighted by cw[j] (CMA δw, no division)
 __global__ void __launch_bounds__(256) k_gather_mean(const double* __restrict__ X, const int32_t* __restrict__ idx, const double* __restrict__ cw,
                                                      double* __restrict__ mu, size_t mu_stride, int cs, int K, int m, int divide, const int* active) {

@@ -230,12 +230,14 @@ void launch_nes_potri(const double* L, size_t Lstride, double* X, double* S, int
     nes_gemm(g, B, n, active, s);
 }
 
-// ---- U ← U - (sf/K) S g -----------------------------------------------------------------------------------
+// ---- U ← U - (sf/K) S g  (Scale = const double*: per-slot step_factor, scale[b] = sf_b / K) -----------------
+template <class Scale>
 __global__ void __launch_bounds__(256) k_nes_u_update(const double* __restrict__ S, size_t Sstride, const double* __restrict__ g, double* __restrict__ U,
-                                                      int n, double scale, const int* active) {
+                                                      int n, Scale scale_arg, const int* active) {
     MPOPIS_HI_PRIO();
     const int b = blockIdx.y;
     if (!active[b]) return;
+    const double scale = slot_val(scale_arg, b);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double* Sb = S + (size_t)b * Sstride;
@@ -245,35 +247,19 @@ __global__ void __launch_bounds__(256) k_nes_u_update(const double* __restrict__
     U[(size_t)b * n + i] -= scale * acc;
 }
 
-// per-slot step_factor (mpopis_set_slot_hyper): scale[b] = sf_b / K
-__global__ void __launch_bounds__(256) k_nes_u_update_slots(const double* __restrict__ S, size_t Sstride, const double* __restrict__ g, double* __restrict__ U,
-                                                            int n, const double* __restrict__ scale, const int* active) {
-    MPOPIS_HI_PRIO();
-    const int b = blockIdx.y;
-    if (!active[b]) return;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const double* Sb = S + (size_t)b * Sstride;
-    const double* gb = g + (size_t)b * n;
-    double acc = 0.0;
-    for (int j = 0; j < n; ++j) acc = fma(Sb[i + (size_t)j * n], gb[j], acc);
-    U[(size_t)b * n + i] -= scale[b] * acc;
-}
-
 // The whole update of iteration n < N (after launch_nes_break).  S: Σ^-1 of the iteration (stride 0 at n = 1: Σ0^-1), Ain / Aout: A′ before / after,
 // Sig: Σ′ out, T and M: B x cs x cs scratch (M ends holding G).
 void launch_nes_update(const double* E, const double* cost, double* part, int ksplit, const double* S, size_t Sstride, double* M, double* T,
                        double* g, double* Csum, const double* Ain, size_t Astride, double* Aout, double* Sig, double* U,
-                       int B, int cs, int K, double step_factor, const int* active, hipStream_t s, const double* a_scale, const double* u_scale) {
+                       int B, int cs, int K, SlotVal a_scale, SlotVal u_scale, const int* active, hipStream_t s) {
     const size_t nn = (size_t)cs * cs;
     launch_nes_scatter(E, cost, part, M, g, Csum, B, cs, K, ksplit, active, s);
     nes_gemm(NesGemm{S, Sstride, 0, M, nn, 0, nullptr, 0, T, nn, 1.0, nullptr, 0.0, nullptr, 0}, B, cs, active, s);            // T = S M
     nes_gemm(NesGemm{T, nn, 0, S, Sstride, 0, S, Sstride, M, nn, 1.0, nullptr, -1.0, Csum, 0}, B, cs, active, s);              // G = T S - C S
-    // (per-slot step_factor: a_scale[b] = -sf_b / K² and u_scale[b] = sf_b / K, formed on the host like the two scalars)
-    nes_gemm(NesGemm{Ain, Astride, 0, M, nn, 0, Ain, Astride, Aout, nn, a_scale ? 1.0 : -step_factor / ((double)K * K), a_scale, 1.0, nullptr, 0}, B, cs, active, s);   // A′ - (sf/K²) A′ G
+    nes_gemm(NesGemm{Ain, Astride, 0, M, nn, 0, Ain, Astride, Aout, nn, a_scale.per_slot ? 1.0 : a_scale.v, a_scale.per_slot, 1.0, nullptr, 0}, B, cs, active, s);   // A′ - (sf/K²) A′ G
     nes_gemm(NesGemm{Aout, nn, 1, Aout, nn, 0, nullptr, 0, Sig, nn, 1.0, nullptr, 0.0, nullptr, 1}, B, cs, active, s);        // Σ′ = A′' A′
-    if (u_scale) hipLaunchKernelGGL(k_nes_u_update_slots, dim3((cs + 255) / 256, B), dim3(256), 0, s, S, Sstride, g, U, cs, u_scale, active);
-    else hipLaunchKernelGGL(k_nes_u_update, dim3((cs + 255) / 256, B), dim3(256), 0, s, S, Sstride, g, U, cs, step_factor / K, active);
+    if (u_scale.per_slot) hipLaunchKernelGGL(k_nes_u_update<const double*>, dim3((cs + 255) / 256, B), dim3(256), 0, s, S, Sstride, g, U, cs, u_scale.per_slot, active);
+    else hipLaunchKernelGGL(k_nes_u_update<double>, dim3((cs + 255) / 256, B), dim3(256), 0, s, S, Sstride, g, U, cs, u_scale.v, active);
 }
 
 }  // namespace mpopis

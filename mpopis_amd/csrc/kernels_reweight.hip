@@ -33,66 +33,14 @@ __device__ __forceinline__ double block_reduce(double v, double* sh) {
     return r;
 }
 
-// k_weights_slots below is a copy of this body that reads -1/λ per slot: a fix here belongs there too.
+// Lam = double: one -1/λ for the batch; const double*: slot b weighs with -1/λ_b (mpopis_set_slot_hyper), formed on the host like the scalar.
+template <class Lam>
 __global__ void __launch_bounds__(1024) k_weights(const double* __restrict__ cost, double* __restrict__ w, int K,
-                                                  double neg_inv_lambda, const int* active, int* status, double* __restrict__ wsum) {
+                                                  Lam neg_inv_lambda_arg, const int* active, int* status, double* __restrict__ wsum) {
     MPOPIS_HI_PRIO();
     const int b = blockIdx.x;
     if (active && !active[b]) return;
-    __shared__ double sh[16];
-    const double* c = cost + (size_t)b * K;
-    double* wo = w + (size_t)b * K;
-    double m = INFINITY;
-    bool bad = false;
-    if (K <= 8 * (int)blockDim.x) {
-        // the slot's costs fit the workgroup's registers (<= 8 per thread): one read of the costs, one write of the weights, instead of three
-        // passes through memory with a dependent round trip each; same per-thread summation order as the loops below (bit-identical)
-        double cv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int k = threadIdx.x + u * blockDim.x; cv[u] = (k < K) ? c[k] : INFINITY; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int k = threadIdx.x + u * blockDim.x; if (k < K) { m = fmin(m, cv[u]); bad |= !(fabs(cv[u]) < INFINITY); } }
-        m = block_reduce<true>(m, sh);                                         // ρ = minimum(costs)
-        double s = 0.0;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int k = threadIdx.x + u * blockDim.x; if (k < K) { cv[u] = exp(neg_inv_lambda * (cv[u] - m)); s += cv[u]; } }
-        s = block_reduce<false>(s, sh);                                        // η
-        double t = 0.0;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int k = threadIdx.x + u * blockDim.x; if (k < K) { const double v = cv[u] / s; wo[k] = v; t += v; } }
-        if (wsum) {
-            t = block_reduce<false>(t, sh);
-            if (threadIdx.x == 0) wsum[b] = t;
-        }
-        if (bad && status) status_raise(&status[b], MPOPIS_ERR_ACTION);
-        return;
-    }
-    for (int k = threadIdx.x; k < K; k += blockDim.x) { const double v = c[k]; m = fmin(m, v); bad |= !(fabs(v) < INFINITY); }
-    m = block_reduce<true>(m, sh);                                             // ρ = minimum(costs)
-    double s = 0.0;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        const double e = exp(neg_inv_lambda * (c[k] - m));                     // exp(-1/λ * (c - ρ))
-        wo[k] = e; s += e;
-    }
-    s = block_reduce<false>(s, sh);                                            // η
-    double t = 0.0;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) { const double v = wo[k] / s; wo[k] = v; t += v; }
-    if (wsum) {                                                                // Σ_k w_k of the normalised weights (≈ 1), for the scatter finish
-        t = block_reduce<false>(t, sh);
-        if (threadIdx.x == 0) wsum[b] = t;
-    }
-    if (bad && status) status_raise(&status[b], MPOPIS_ERR_ACTION);               // non-finite cost <=> NaN action (car_racing.jl:239)
-}
-
-// The per-slot form (mpopis_set_slot_hyper): slot b weighs with neg_inv_lambda_b[b] = -1/λ_b, formed on the host like the scalar above.  A copy of
-// k_weights, not a shared inlined body: with one, the compiler schedules k_weights differently, and the kernel that runs on every handle today
-// keeps its instruction stream.
-__global__ void __launch_bounds__(1024) k_weights_slots(const double* __restrict__ cost, double* __restrict__ w, int K,
-                                                  const double* __restrict__ neg_inv_lambda_b, const int* active, int* status, double* __restrict__ wsum) {
-    MPOPIS_HI_PRIO();
-    const int b = blockIdx.x;
-    if (active && !active[b]) return;
-    const double neg_inv_lambda = neg_inv_lambda_b[b];
+    const double neg_inv_lambda = slot_val(neg_inv_lambda_arg, b);
     __shared__ double sh[16];
     const double* c = cost + (size_t)b * K;
     double* wo = w + (size_t)b * K;
@@ -143,11 +91,9 @@ WeightsForm weights_form(int K) {                                               
     if (K <= 8 * weights_block(K)) return weights_block(K) == 1024 ? WEIGHTS_REG_1024 : WEIGHTS_REG_256;
     return WEIGHTS_3PASS_1024;                                                   // (K > 8192: the block is 1024 there)
 }
-void launch_weights(const double* cost, double* w, int B, int K, double lambda, const int* active, int* status, hipStream_t s, double* wsum) {
-    hipLaunchKernelGGL(k_weights, dim3(B), dim3(weights_block(K)), 0, s, cost, w, K, -1 / lambda, active, status, wsum);
-}
-void launch_weights_slots(const double* cost, double* w, int B, int K, const double* neg_inv_lambda, const int* active, int* status, hipStream_t s, double* wsum) {
-    hipLaunchKernelGGL(k_weights_slots, dim3(B), dim3(weights_block(K)), 0, s, cost, w, K, neg_inv_lambda, active, status, wsum);
+void launch_weights(const double* cost, double* w, int B, int K, SlotVal nil, const int* active, int* status, hipStream_t s, double* wsum) {
+    if (nil.per_slot) hipLaunchKernelGGL(k_weights<const double*>, dim3(B), dim3(weights_block(K)), 0, s, cost, w, K, nil.per_slot, active, status, wsum);
+    else hipLaunchKernelGGL(k_weights<double>, dim3(B), dim3(weights_block(K)), 0, s, cost, w, K, nil.v, active, status, wsum);
 }
 
 __global__ void __launch_bounds__(256) k_wmean(const double* __restrict__ E, const double* __restrict__ w,

@@ -20,10 +20,14 @@ BREAK_THRESHOLD = 10e-3                                    # the reference write
 # ---- the harness's files ---------------------------------------------------------------------------------------------------------------
 def pack_case(op, B, K, active, m_elite=0, no_ws=False, lam=1.0, status0=None, cost=None, w=None, accept=None, alias=None, di=None, du=None,
               di_stride=0, log_stride=0):
+    """lam: one λ, or (OP_WEIGHTS) a pair (λ_even, λ_odd): the per-slot mode, even slots weigh with the first and odd slots with the second"""
+    lam_pair = np.ndim(lam) > 0
+    lam_even, lam_odd = (float(lam[0]), float(lam[1])) if lam_pair else (float(lam), 0.0)
+    assert not lam_pair or (op == OP_WEIGHTS and len(lam) == 2)
     active = np.ascontiguousarray(active, dtype=np.int32)
     status0 = np.zeros(B, dtype=np.int32) if status0 is None else np.ascontiguousarray(status0, dtype=np.int32)
     assert active.shape == (B,) and status0.shape == (B,)
-    out = [MAGIC_IN, struct.pack("<7q", op, B, K, m_elite, 1 if no_ws else 0, di_stride, log_stride), struct.pack("<2d", lam, 0.0),
+    out = [MAGIC_IN, struct.pack("<7q", op, B, K, m_elite, (1 if no_ws else 0) | (2 if lam_pair else 0), di_stride, log_stride), struct.pack("<2d", lam_even, lam_odd),
            active.tobytes(), status0.tobytes()]
     f64 = lambda x, n: _arr(x, np.float64, n).tobytes()
     i32 = lambda x, n: _arr(x, np.int32, n).tobytes()
@@ -46,7 +50,9 @@ def unpack_case(buf):
     """inverse of pack_case (what the harness parses)"""
     assert buf[:8] == MAGIC_IN
     op, B, K, m_elite, flags, di_stride, log_stride = struct.unpack_from("<7q", buf, 8)
-    lam, _ = struct.unpack_from("<2d", buf, 64)
+    lam, lam_odd = struct.unpack_from("<2d", buf, 64)
+    if flags & 2:
+        lam = (lam, lam_odd)
     off = 80
     def take(dt, n):
         nonlocal off

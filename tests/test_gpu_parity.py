@@ -285,9 +285,16 @@ def test_env_step_and_errors(eng_mod, oracle, track):
     with pytest.raises(MPOPISError) as ei:
         eng.env_step([[1.5, 0.0]])                         # "Action is not in action space" car_racing.jl:239
     assert ei.value.code == -3
+    Z = np.random.default_rng(5).standard_normal((1, 1, 64, 10))
+    U0 = eng.get_U()
+    before = eng.policy_step(Z)
     with pytest.raises(MPOPISError) as ei:
         eng.set_Sigma(np.array([[1.0, 2.0], [2.0, 1.0]]))  # PosDefException
     assert ei.value.code == -2
+    eng.set_U(U0)                                          # a refused set_Sigma leaves the handle as it was: the same step gives the same bits
+    after = eng.policy_step(Z)
+    for key in ("control", "cost", "weights"):
+        assert np.array_equal(before[key], after[key]), key
     with pytest.raises(MPOPISError) as ei:
         eng.set_Sigma(np.eye(3))                           # "Covariance matrix size problem" :79
     assert ei.value.code == -1

@@ -303,6 +303,7 @@ def _weights_form(K):
 
 
 def _run_weights(exe, tmp_path, K, lam, vecs):
+    """lam: one λ for every slot, or a pair (λ_even, λ_odd) = the per-slot form of the same launcher"""
     B = len(vecs)
     cost = np.stack([np.zeros(K) if v is None else v for v in vecs])
     active = np.array([0 if v is None else 1 for v in vecs], dtype=np.int32)
@@ -353,3 +354,41 @@ def test_weights_flag_a_non_finite_cost_for_its_slot_only(harness, tmp_path, K, 
     assert r["status"][:3].tolist() == [0, S.ERR_ACTION, 0]
     for s in (0, 2):
         assert np.array_equal(_bits(r["w"][s]), _bits(clean["w"][s])) and r["wsum"][s] == clean["wsum"][s]
+
+
+LAM_EVEN, LAM_ODD = 10.0, 0.7
+
+
+def _assert_slot_bits(per_slot, scalar, b):
+    assert np.array_equal(_bits(per_slot["w"][b]), _bits(scalar["w"][b])), b
+    assert np.array_equal(_bits(per_slot["wsum"][b:b + 1]), _bits(scalar["wsum"][b:b + 1])), b
+    assert per_slot["status"][b] == scalar["status"][b], b
+
+
+@pytest.mark.parametrize("K", [1, 256, 1024, 8192, 8193])
+def test_weights_per_slot_lambda_is_the_scalar_run_of_that_lambda(harness, tmp_path, K):
+    """The per-slot instantiation of k_weights differs from the scalar one by the load of -1/λ_b alone: each active slot's w and wsum are
+    bit-equal to a scalar run with that slot's λ (smallest K, a full 256-thread register form, the first and the last 1024-thread register form,
+    the first three-pass form).  _run_weights checks the form, the inactive slot and the guards of every run."""
+    rng = np.random.default_rng(3000 + K)
+    a, b, c = (rng.standard_normal(K) * 20.0 + 100.0 for _ in range(3))
+    slots = [a, b, c, None]
+    per_slot = _run_weights(harness, tmp_path, K, (LAM_EVEN, LAM_ODD), slots)
+    scalar = [_run_weights(harness, tmp_path, K, lam, slots) for lam in (LAM_EVEN, LAM_ODD)]
+    for s in range(3):
+        _assert_slot_bits(per_slot, scalar[s % 2], s)
+        assert per_slot["status"][s] == 0
+    if K > 1:                                                                          # the two λ do weigh differently: the runs are not one run
+        assert not np.array_equal(_bits(scalar[0]["w"][0]), _bits(scalar[1]["w"][0]))
+
+
+def test_weights_per_slot_lambda_flags_a_nan_cost_for_its_slot_only(harness, tmp_path):
+    K = 1000
+    rng = np.random.default_rng(3000 + K)
+    a, b, c = (rng.standard_normal(K) * 20.0 + 100.0 for _ in range(3))
+    clean = _run_weights(harness, tmp_path, K, (LAM_EVEN, LAM_ODD), [a, b, c, None])
+    hurt = b.copy(); hurt[K // 2] = np.nan
+    r = _run_weights(harness, tmp_path, K, (LAM_EVEN, LAM_ODD), [a, hurt, c, None])
+    assert clean["status"][:3].tolist() == [0, 0, 0] and r["status"][:3].tolist() == [0, S.ERR_ACTION, 0]
+    for s in (0, 2):
+        _assert_slot_bits(r, clean, s)

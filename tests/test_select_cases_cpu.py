@@ -2,6 +2,7 @@
 holds the generators both files share): the literal transcription of make_alias_table! reproduces the oracle bit for bit and the case list reaches the
 loop's `dry` exit, leftover smalls, chains of exhausted larges longer than a 64-entry batch and exact ties; the early-break vectors sit on the side of
 10e-3 they are named for; the weight inputs meet the test's tolerance with the oracle's own double arithmetic; the harness's files round-trip."""
+import struct
 import numpy as np
 import pytest
 from tests.helpers import select_cases as S
@@ -114,7 +115,14 @@ def test_case_files_round_trip():
     assert (c["op"], c["B"], c["K"], c["m_elite"], c["no_ws"]) == (S.OP_SORT, B, K, 7, True)
     assert np.array_equal(_bits(c["cost"]), _bits(cost).reshape(B, K)) and c["active"].tolist() == [1, 0, 1]
     c = S.unpack_case(S.pack_case(S.OP_WEIGHTS, B, K, [1, 1, 0], lam=1e-6, status0=[0, 0, S.POISON_I32], cost=cost))
-    assert c["lam"] == 1e-6 and c["status0"].tolist() == [0, 0, S.POISON_I32]
+    assert c["lam"] == 1e-6 and c["status0"].tolist() == [0, 0, S.POISON_I32] and not c["no_ws"]
+    # per-slot λ: the second double of the header and bit 1 of flags, beside bit 0 and without disturbing it
+    for no_ws in (False, True):
+        buf = S.pack_case(S.OP_WEIGHTS, B, K, [1, 1, 0], lam=(10.0, 0.7), no_ws=no_ws, cost=cost)
+        assert struct.unpack_from("<q", buf, 8 + 4 * 8)[0] == (2 | int(no_ws)) and struct.unpack_from("<2d", buf, 64) == (10.0, 0.7)
+        c = S.unpack_case(buf)
+        assert c["lam"] == (10.0, 0.7) and c["no_ws"] == no_ws and np.array_equal(_bits(c["cost"]), _bits(cost).reshape(B, K))
+    assert struct.unpack_from("<2d", S.pack_case(S.OP_WEIGHTS, B, K, [1, 1, 0], lam=3.0, cost=cost), 64) == (3.0, 0.0)
     acc, al = rng.random((B, K)), rng.integers(0, K, (B, K))
     di, du = rng.integers(0, K, (B, K + 5)), rng.random((B, K + 5))
     c = S.unpack_case(S.pack_case(S.OP_ALIAS_SAMPLE, B, K, [1, 1, 1], accept=acc, alias=al, di=di, du=du, di_stride=K + 5, log_stride=K + 3))

@@ -5,7 +5,7 @@
 //
 // case file (little endian; layout shared with tests/helpers/select_cases.py):
 //   int64  hdr[8]  = { magic 'SELCASE1', op, B, K, m_elite, flags, di_stride, log_stride }      flags bit 0: run WITHOUT the workspaces (nullptr)
-//   double par[2]  = { lambda, unused }
+//   double par[2]  = { lambda, lambda_odd }         flags bit 1 (op 3): per-slot λ -- even slots weigh with lambda, odd slots with lambda_odd
 //   int32  active[B], status0[B]            (status0: what status[] holds before the launch; the test poisons the inactive slot's entry itself)
 //   op 0 sort / 4 CE sort: double cost[B K]
 //   op 1 alias build:      double w[B K]
@@ -49,7 +49,7 @@ int main(int argc, char** argv) {
     if (!rd(fi, hdr, 8) || hdr[0] != kMagicIn) { printf("bad case header\n"); return 2; }
     const int op = (int)hdr[1]; const long long B = hdr[2], K = hdr[3], m_elite = hdr[4], flags = hdr[5], di_stride = hdr[6], log_stride = hdr[7];
     if (B < 1 || B > 64 || K < 1 || K > (1 << 20) || m_elite < 0 || m_elite > K || op < 0 || op > 4) { printf("case out of range\n"); return 2; }
-    const bool no_ws = flags & 1;
+    const bool no_ws = flags & 1, lam_per_slot = flags & 2;
     const size_t BK = (size_t)B * K;
     if (!rd(fi, par, 2) || !rd(fi, active, B) || !rd(fi, status0, B)) { printf("short case file\n"); return 2; }
     std::vector<double> f0, f1; std::vector<int32_t> i0, i1;
@@ -106,7 +106,14 @@ int main(int argc, char** argv) {
         double *d_cost, *d_w, *d_wsum; int* d_status;
         CK(dupload(&d_cost, f0)); CK(dpoison(&d_w, BK + kGuard)); CK(dpoison(&d_wsum, B)); CK(dupload(&d_status, status0));
         form = weights_form((int)K);
-        launch_weights(d_cost, d_w, (int)B, (int)K, par[0], d_active, d_status, s, d_wsum);
+        SlotVal nil{-1 / par[0], nullptr};
+        if (lam_per_slot) {
+            std::vector<double> nil_b(B);
+            for (long long b = 0; b < B; ++b) nil_b[b] = -1 / par[b & 1];
+            double* d_nil; CK(dupload(&d_nil, nil_b));
+            nil.per_slot = d_nil;
+        }
+        launch_weights(d_cost, d_w, (int)B, (int)K, nil, d_active, d_status, s, d_wsum);
         CK(hipGetLastError()); CK(hipStreamSynchronize(s));
         CK(dfetch(of0, d_w, BK + kGuard)); CK(dfetch(of1, d_wsum, B)); CK(dfetch(oi0, d_status, B));
     }
