@@ -1,16 +1,11 @@
 // engine.h -- internal declarations shared by the HIP translation units of libmpopis_hip.so.
 //
-// Data layout in HBM (per handle, B trial slots, all FP64 unless noted):
-//   x      [B][ss]        resident real-env state (+ t[B], done[B] int32)
-//   U      [B][cs]        pol.U (nominal control, step-major like the reference)
-//   Ucur   [B][cs]        AIS mean inside calculate_trajectory_costs (pol.U rebinding)
+// Data layout in HBM: per handle, B trial slots, every per-slot buffer [B][...], FP64 unless its type says otherwise.  The record of the buffers
+// and their per-slot extents is the declaration table in create_handle (engine_api.hip), from which the slot views are derived too.
 //   E      [B][cs][K]     noise, ROW-MAJOR BY CONTROL ROW (K fastest).  The reference stores E as
 //                         cs x K column-major (sample k contiguous); here lanes = samples, so the
 //                         transpose makes every rollout-kernel load and every reduction over k
 //                         coalesced.  The C ABI transposes on upload/download.
-//   Sigma  [B][n][n]      proposal covariance, column-major (n = as for :mppi, cs otherwise)
-//   Lchol  [B][n][n]      its lower Cholesky factor
-//   cost, w [B][K]; status[B] int32; misc per-trial scalars.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -75,11 +75,20 @@ __global__ void k_call_out(CallBox m, const double* control, const double* U, co
 static void fill_i32(int* p, int v, size_t n, hipStream_t s) { hipLaunchKernelGGL(k_fill_i32, dim3((n + 255) / 256), dim3(256), 0, s, p, v, n); }
 static void copy_f64(const double* s_, double* d, size_t n, hipStream_t s) { hipLaunchKernelGGL(k_copy_f64, dim3((n + 255) / 256), dim3(256), 0, s, s_, d, n); }
 
-template <class T> static int dalloc(mpopis_handle* h, T** p, size_t n) {
-    HIPCHK(h, hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
-    HIPCHK(h, hipMemsetAsync(*p, 0, std::max<size_t>(n, 1) * sizeof(T), h->stream));
-    h->allocs.push_back((void*)*p);
+// the one place the handle's buffers come from (shared_alloc / slot_alloc, engine_handle.h): zero-filled on the stream, owned until mpopis_destroy
+int mpopis_handle::dev_alloc(void** p, size_t bytes) {
+    HIPCHK(this, hipMalloc(p, bytes));
+    allocs.push_back(*p);
+    HIPCHK(this, hipMemsetAsync(*p, 0, bytes, stream));
     return 0;
+}
+
+// a setup call that replaces what queued work may still read: wait for everything the handle has queued, on the part-chain streams too
+static int quiesce(mpopis_handle* h) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
+    return MPOPIS_OK;
 }
 
 static const char* kClassNames[] = {"rollout", "sample", "potrf", "reweight", "moments", "select", "other"};
@@ -133,10 +142,7 @@ static hipError_t wait_step(mpopis_handle* h) {
 static int fold_status(mpopis_handle* h, const int* per_slot) {
     int st = 0;
     for (int b = 0; b < h->B; ++b) st = mpopis::worse_status(st, per_slot[b]);
-    if (st == MPOPIS_ERR_NOT_PD) h->err = "PosDefException: proposal covariance is not positive definite";
-    else if (st == MPOPIS_ERR_ACTION) h->err = "Action is not in action space (non-finite control/cost)";
-    else if (st == MPOPIS_ERR_NUMERIC) h->err = "cmamppi: Σ^-0.5 δw could not be formed (non-finite covariance, trace or δw)";
-    return st;
+    return h->report_status(st);
 }
 
 static int sync_status(mpopis_handle* h) {
@@ -192,6 +198,8 @@ static int check_policy_config(const mpopis_config* cfg, int as) {
 }
 
 static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle** out);
+// a create call that fails half-way (hipStreamCreate under many handles is a realistic one) must not leak the handle and what it already owns
+static int fail_create(mpopis_handle* h, int code, const std::string& msg) { g_create_error = msg; mpopis_destroy(h); return code; }
 
 // hipModuleLoadData takes no length: a buffer whose own tables point past nbytes would be read beyond the caller's memory.  Little-endian ELF64
 // (the section header table and, through it, every section must lie inside) or a clang offload bundle (every entry must; an ELF entry is checked too).
@@ -257,22 +265,21 @@ int mpopis_create_custom(const mpopis_config* cfg_in, const void* code_object, u
     if (const int rc = check_policy_config(&cfg, action_size)) return rc;
     mpopis_handle* h = nullptr;
     if (const int rc = create_handle(&cfg, action_size, state_size, &h)) return rc;
-    auto fail = [&](int code, const std::string& msg) { g_create_error = msg; mpopis_destroy(h); return code; };
     // the module belongs to the handle (two handles with different code objects coexist); mpopis_destroy unloads it
     hipError_t e = hipModuleLoadData(&h->custom.module, code_object);
-    if (e != hipSuccess) { h->custom.module = nullptr; return fail(MPOPIS_ERR_ARG, std::string("mpopis_create_custom: the code object does not load on this device (hipModuleLoadData: ") + hipGetErrorString(e) + "); build it for gfx950"); }
+    if (e != hipSuccess) { h->custom.module = nullptr; return fail_create(h, MPOPIS_ERR_ARG, std::string("mpopis_create_custom: the code object does not load on this device (hipModuleLoadData: ") + hipGetErrorString(e) + "); build it for gfx950"); }
     hipDeviceptr_t abi_ptr = nullptr; size_t abi_bytes = 0;
     int32_t abi[4] = {0, 0, 0, 0};
     if (hipModuleGetGlobal(&abi_ptr, &abi_bytes, h->custom.module, "mpopis_env_abi") != hipSuccess || abi_bytes != sizeof abi ||
         hipMemcpyDtoH(abi, abi_ptr, sizeof abi) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(MPOPIS_ERR_ARG, "mpopis_create_custom: the code object has no constant mpopis_env_abi (was it built with MPOPIS_DEFINE_ENV of mpopis_env.h?)");
+        return fail_create(h, MPOPIS_ERR_ARG, "mpopis_create_custom: the code object has no constant mpopis_env_abi (was it built with MPOPIS_DEFINE_ENV of mpopis_env.h?)");
     }
     if (abi[0] != MPOPIS_ENV_SDK_VERSION || abi[1] != state_size || abi[2] != action_size || abi[3] != nparams) {
         char buf[256];
         snprintf(buf, sizeof buf, "mpopis_create_custom: the code object was built with SDK version %d for state_size %d, action_size %d, nparams %d; the call says version %d, %d, %d, %d",
                  abi[0], abi[1], abi[2], abi[3], MPOPIS_ENV_SDK_VERSION, state_size, action_size, nparams);
-        return fail(MPOPIS_ERR_ARG, buf);
+        return fail_create(h, MPOPIS_ERR_ARG, buf);
     }
     // an env with a table (MPOPIS_DEFINE_ENV_TABLE) says so with a second constant and has four kernels under names of their own
     hipDeviceptr_t tab_ptr = nullptr; size_t tab_bytes = 0;
@@ -280,13 +287,13 @@ int mpopis_create_custom(const mpopis_config* cfg_in, const void* code_object, u
     if (hipModuleGetGlobal(&tab_ptr, &tab_bytes, h->custom.module, "mpopis_env_table_abi") == hipSuccess) {
         if (tab_bytes != sizeof tab_abi || hipMemcpyDtoH(tab_abi, tab_ptr, sizeof tab_abi) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(MPOPIS_ERR_ARG, "mpopis_create_custom: the code object's constant mpopis_env_table_abi cannot be read (two int32 expected)");
+            return fail_create(h, MPOPIS_ERR_ARG, "mpopis_create_custom: the code object's constant mpopis_env_table_abi cannot be read (two int32 expected)");
         }
         if (tab_abi[0] != MPOPIS_ENV_TABLE_VERSION || tab_abi[1] < 0 || tab_abi[1] > kEnvTableLdsMaxDoubles) {
             char buf[256];
             snprintf(buf, sizeof buf, "mpopis_create_custom: the code object was built with env table version %d (LDS table limit %d doubles); this library knows version %d and stages at most %d",
                      tab_abi[0], tab_abi[1], MPOPIS_ENV_TABLE_VERSION, kEnvTableLdsMaxDoubles);
-            return fail(MPOPIS_ERR_ARG, buf);
+            return fail_create(h, MPOPIS_ERR_ARG, buf);
         }
         h->custom.has_table = true;
         h->custom.table_lds_doubles = tab_abi[1];
@@ -301,13 +308,13 @@ int mpopis_create_custom(const mpopis_config* cfg_in, const void* code_object, u
     for (const auto& k : kernels)
         if (hipModuleGetFunction(k.fn, h->custom.module, k.name) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(MPOPIS_ERR_ARG, std::string("mpopis_create_custom: the code object has no kernel ") + k.name);
+            return fail_create(h, MPOPIS_ERR_ARG, std::string("mpopis_create_custom: the code object has no kernel ") + k.name);
         }
-    if (dalloc(h, &h->custom.d_params, (size_t)nparams)) return fail(MPOPIS_ERR_HIP, h->err);      // zeros until mpopis_set_env_params
+    if (h->shared_alloc(h->custom.d_params, (size_t)nparams)) return fail_create(h, MPOPIS_ERR_HIP, h->err);      // zeros until mpopis_set_env_params
     h->custom.nparams = nparams;
     h->custom_reset.assign((size_t)state_size, 0.0);
     if (reset_state) memcpy(h->custom_reset.data(), reset_state, sizeof(double) * state_size);
-    if (mpopis_reset(h) != 0) return fail(MPOPIS_ERR_HIP, h->err);
+    if (mpopis_reset(h) != 0) return fail_create(h, MPOPIS_ERR_HIP, h->err);
     *out = h;
     return MPOPIS_OK;
 }
@@ -320,27 +327,18 @@ static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_error = "bad device ordinal"; return MPOPIS_ERR_ARG; }
     mpopis_handle* h = new mpopis_handle();
     h->cfg = *cfg;
-    // a failure half-way (hipStreamCreate under many handles is a realistic one) must not leak the handle and what it already owns
-#define CREATECHK(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            char buf_[512];                                                                     \
-            snprintf(buf_, sizeof buf_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            g_create_error = buf_;                                                              \
-            mpopis_destroy(h);                                                                  \
-            return MPOPIS_ERR_HIP;                                                              \
-        }                                                                                       \
-    } while (0)
-    CREATECHK(hipSetDevice(cfg->device));
-    CREATECHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    CREATECHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    for (int i = 0; i < mpopis_handle::kMaxSplit - 1; ++i) {
-        CREATECHK(hipStreamCreateWithFlags(&h->xstream[i], hipStreamNonBlocking));
-        CREATECHK(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
-        CREATECHK(hipEventCreateWithFlags(&h->ev_skew[i], hipEventDisableTiming));
-    }
-#undef CREATECHK
+    auto streams_and_events = [&]() -> int {
+        HIPCHK(h, hipSetDevice(cfg->device));
+        HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+        for (int i = 0; i < mpopis_handle::kMaxSplit - 1; ++i) {
+            HIPCHK(h, hipStreamCreateWithFlags(&h->xstream[i], hipStreamNonBlocking));
+            HIPCHK(h, hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
+            HIPCHK(h, hipEventCreateWithFlags(&h->ev_skew[i], hipEventDisableTiming));
+        }
+        return MPOPIS_OK;
+    };
+    if (streams_and_events()) return fail_create(h, MPOPIS_ERR_HIP, h->err);
     if (const char* e = getenv("MPOPIS_DEBUG_LAUNCH")) h->debug_launch = atoi(e) != 0;
     if (const char* e = getenv("MPOPIS_NSPLIT")) { h->nsplit = std::max(1, std::min((int)mpopis_handle::kMaxSplit, atoi(e))); h->split_auto = false; h->split_pinned = true; }   // experiments / profiling: pins the schedule, mpopis_set_overlap is then ignored
     h->B = cfg->batch; h->B_full = cfg->batch; h->K = cfg->num_samples; h->T = cfg->horizon;
@@ -358,47 +356,51 @@ static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle
     h->env.track = Track{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr};
     h->env.custom = cfg->env_kind == MPOPIS_ENV_CUSTOM ? &h->custom : nullptr;
     const int B = h->B, K = h->K, cs = h->cs;
-    const size_t nn = (size_t)cs * cs;
-    int rc = 0;
-    rc |= dalloc(h, &h->d_x, (size_t)B * h->ss); rc |= dalloc(h, &h->d_xext, (size_t)B * kMaxCars * kCarExt); rc |= dalloc(h, &h->d_t, B); rc |= dalloc(h, &h->d_done, B);
-    rc |= dalloc(h, &h->d_U, (size_t)B * cs); rc |= dalloc(h, &h->d_Ucur, (size_t)B * cs); rc |= dalloc(h, &h->d_Uin, (size_t)B * cs);
-    rc |= dalloc(h, &h->S0sh.Sigma, nn); rc |= dalloc(h, &h->d_Sig, (size_t)B * nn + kInvsqrtPadDoubles); rc |= dalloc(h, &h->d_L, (size_t)B * nn);
-    rc |= dalloc(h, &h->S0sh.L, nn); rc |= dalloc(h, &h->d_tmpS, (size_t)B * nn);
-    if (sample_trmm_fusable(cs)) { rc |= dalloc(h, &h->S0sh.Lp, potrf_panel_doubles(cs)); rc |= dalloc(h, &h->d_Lp, (size_t)B * potrf_panel_doubles(cs)); }
-    rc |= dalloc(h, &h->d_coop_flags, potrf_coop_flag_words(B, cs)); rc |= dalloc(h, &h->d_potrf_redo, B); rc |= dalloc(h, &h->d_lan_redo, B); rc |= dalloc(h, &h->d_coop_timeouts, 1);
-    rc |= dalloc(h, &h->d_Z, (size_t)B * cs * K); rc |= dalloc(h, &h->d_E, (size_t)B * cs * K);
-    rc |= dalloc(h, &h->d_cost, (size_t)B * K); rc |= dalloc(h, &h->d_w, (size_t)B * K);
-    rc |= dalloc(h, &h->d_wn, (size_t)B * cs); rc |= dalloc(h, &h->d_mu, (size_t)B * cs); rc |= dalloc(h, &h->d_gvec, (size_t)B * cs);
-    rc |= dalloc(h, &h->d_dscale, (size_t)B * cs); rc |= dalloc(h, &h->d_dscale0, (size_t)cs);
-    rc |= dalloc(h, &h->d_control, (size_t)B * h->as); rc |= dalloc(h, &h->d_reward, B); rc |= dalloc(h, &h->d_wsum, B); rc |= dalloc(h, &h->d_cmin, B);
-    rc |= dalloc(h, &h->d_status, B); rc |= dalloc(h, &h->d_active, B); rc |= dalloc(h, &h->d_iters, B); rc |= dalloc(h, &h->d_iters_acc, B);
-    rc |= dalloc(h, &h->d_seeds, B); rc |= dalloc(h, &h->d_rng_tab, mpopis::kRngTabDoubles);      // philox.h
-    rc |= dalloc(h, &h->d_order, (size_t)B * K); rc |= dalloc(h, &h->d_resi, (size_t)B * K); rc |= dalloc(h, &h->d_resu, (size_t)B * K);
-    rc |= dalloc(h, &h->d_accept, (size_t)B * K); rc |= dalloc(h, &h->d_alias, (size_t)B * K); rc |= dalloc(h, &h->d_alias_need, B);
-    if (cfg->policy == MPOPIS_POL_PMCMPPI && K > alias_lds_max_K()) rc |= dalloc(h, &h->d_alias_stack, (size_t)B * 2 * K);      // the global-workspace alias construction
-    rc |= dalloc(h, &h->d_residx_log, (size_t)B * std::max(1, h->N - 1) * K);
+    const size_t nn = (size_t)cs * cs, per = (size_t)cs * K;
     h->ksplit = std::max(1, std::min(std::min(32, K / 128), std::max(1, 512 / B)));   // ~2-4 workgroups per CU in the scatter kernel
     if (const char* e = getenv("MPOPIS_KSPLIT")) h->ksplit = std::max(1, std::min(32, atoi(e)));
-    rc |= dalloc(h, &h->d_part, wcov_mfma_workspace_doubles(B, cs, h->ksplit));
+    // The handle's device buffers: this table is the record of the layout in HBM.  slot(p, n): [B][n] elements, one row per trial slot, moved by
+    // shift_slots with exactly this n (the workspace sizes are their helpers' value for ONE slot; every helper is B times that);
+    // shared(p, n): n elements for the whole batch.  A new per-slot buffer is one more slot(...) line here (or a slot_alloc where it is first
+    // needed) and nothing else.  Matrices are column-major; E / Z are [cs][K] row-major by control row (engine.h).
+    int rc = 0;
+    auto slot = [&](auto*& p, size_t per_slot, size_t pad = 0) { rc |= h->slot_alloc(p, per_slot, pad); };
+    auto shared = [&](auto*& p, size_t n) { rc |= h->shared_alloc(p, n); };
+    slot(h->d_x, h->ss); slot(h->d_xext, kMaxCars * kCarExt); slot(h->d_t, 1); slot(h->d_done, 1);          // resident real-env state
+    slot(h->d_U, cs); slot(h->d_Ucur, cs); slot(h->d_Uin, cs);                                               // pol.U, its rebinding inside a step, U_orig
+    shared(h->S0sh.Sigma, nn); slot(h->d_Sig, nn, kInvsqrtPadDoubles); slot(h->d_L, nn);                     // Σ′ (readable a pad beyond the last slot: kernels_invsqrt.hip), its factor
+    shared(h->S0sh.L, nn); slot(h->d_tmpS, nn);
+    if (sample_trmm_fusable(cs)) { shared(h->S0sh.Lp, potrf_panel_doubles(cs)); slot(h->d_Lp, potrf_panel_doubles(cs)); }
+    slot(h->d_coop_flags, potrf_coop_flag_words(1, cs)); slot(h->d_potrf_redo, 1); slot(h->d_lan_redo, 1); shared(h->d_coop_timeouts, 1);
+    slot(h->d_Z, per); slot(h->d_E, per); slot(h->d_cost, K); slot(h->d_w, K);
+    slot(h->d_wn, cs); slot(h->d_mu, cs); slot(h->d_gvec, cs);
+    slot(h->d_dscale, cs); shared(h->d_dscale0, cs);
+    slot(h->d_control, h->as); slot(h->d_reward, 1); slot(h->d_wsum, 1); slot(h->d_cmin, 1);
+    slot(h->d_status, 1); slot(h->d_active, 1); slot(h->d_iters, 1); slot(h->d_iters_acc, 1);
+    slot(h->d_seeds, 1); shared(h->d_rng_tab, mpopis::kRngTabDoubles);      // philox.h
+    slot(h->d_order, K); slot(h->d_resi, K); slot(h->d_resu, K); slot(h->d_accept, K); slot(h->d_alias, K); slot(h->d_alias_need, 1);
+    if (cfg->policy == MPOPIS_POL_PMCMPPI && K > alias_lds_max_K()) slot(h->d_alias_stack, 2 * (size_t)K);      // the global-workspace alias construction
+    slot(h->d_residx_log, (size_t)std::max(1, h->N - 1) * K);
+    slot(h->d_part, wcov_mfma_workspace_doubles(1, cs, h->ksplit));
     {
         static const int env_fold = [] { const char* e = getenv("MPOPIS_FOLD_WEIGHTS"); return e ? atoi(e) : 1; }();      // 0: keep the separate reweighting launch (A/B)
         h->weights_in_moments = env_fold && cfg->policy == MPOPIS_POL_MUSIGMAAISMPPI && cfg->env_kind == MPOPIS_ENV_CAR && wcov_weights_from_cost_ok(cs, K, h->ksplit);
         h->fold_weights_cfg = h->weights_in_moments;
     }
     if (cfg->policy == MPOPIS_POL_CMAMPPI) {
-        rc |= dalloc(h, &h->d_cma_scal, (size_t)B * 8); rc |= dalloc(h, &h->d_cma_vec, (size_t)B * 3 * cs); rc |= dalloc(h, &h->d_sig2, B);
-        rc |= dalloc(h, &h->d_cma_ws, (size_t)K);
+        slot(h->d_cma_scal, 8); slot(h->d_cma_vec, 3 * (size_t)cs); slot(h->d_sig2, 1); shared(h->d_cma_ws, K);
         h->lan_regions = invsqrt_coop_groups(B, cs);
-        rc |= dalloc(h, &h->d_lanV, invsqrt_workspace_doubles(B, cs, h->lan_regions)); rc |= dalloc(h, &h->d_lan_x, invsqrt_coop_words(B, cs)); rc |= dalloc(h, &h->d_Cdw, (size_t)B * cs);
-        rc |= dalloc(h, &h->d_fro_part, (size_t)B * ((cs + 15) / 16)); rc |= dalloc(h, &h->d_tri_dinv, trtri_dinv_doubles(B, cs)); rc |= dalloc(h, &h->d_fro, B); rc |= dalloc(h, &h->d_lan_m, B); rc |= dalloc(h, &h->d_lan_prep, lanczos_prep_doubles(B)); rc |= dalloc(h, &h->d_tri_cnt, 2 * (size_t)B);
+        slot(h->d_lanV, invsqrt_workspace_doubles(1, cs, h->lan_regions)); slot(h->d_lan_x, invsqrt_coop_words(1, cs)); slot(h->d_Cdw, cs);
+        slot(h->d_fro_part, (cs + 15) / 16); slot(h->d_tri_dinv, trtri_dinv_doubles(1, cs)); slot(h->d_fro, 1); slot(h->d_lan_m, 1); slot(h->d_lan_prep, lanczos_prep_doubles(1)); slot(h->d_tri_cnt, 2);
     }
     if (cfg->policy == MPOPIS_POL_NESMPPI) {
-        rc |= dalloc(h, &h->S0sh.nesA, nn); rc |= dalloc(h, &h->S0sh.nesS, nn); rc |= dalloc(h, &h->d_nesS, (size_t)B * nn);
-        rc |= dalloc(h, &h->d_nesA[0], (size_t)B * nn); rc |= dalloc(h, &h->d_nesA[1], (size_t)B * nn); rc |= dalloc(h, &h->d_nesM, (size_t)B * nn);
-        rc |= dalloc(h, &h->d_nesg, (size_t)B * cs); rc |= dalloc(h, &h->d_nesC, B); rc |= dalloc(h, &h->d_nespart, nes_scatter_workspace_doubles(B, cs, h->ksplit));
+        shared(h->S0sh.nesA, nn); shared(h->S0sh.nesS, nn); slot(h->d_nesS, nn);
+        slot(h->d_nesA[0], nn); slot(h->d_nesA[1], nn); slot(h->d_nesM, nn);
+        slot(h->d_nesg, cs); slot(h->d_nesC, 1); slot(h->d_nespart, nes_scatter_workspace_doubles(1, cs, h->ksplit));
     }
-    if (cfg->log_trajectories) rc |= dalloc(h, &h->d_traj, (size_t)B * K * h->T * h->ss);
-    if (rc) { g_create_error = h->err; mpopis_destroy(h); return MPOPIS_ERR_HIP; }
+    if (cfg->log_trajectories) slot(h->d_traj, (size_t)K * h->T * h->ss);
+    h->slot_view(h->alive_gate, 1);                             // run_trials' gate: d_alive for the length of a step, else null
+    if (rc) return fail_create(h, MPOPIS_ERR_HIP, h->err);
     h->S0 = h->S0sh;
     launch_rng_tab_init(h->d_rng_tab, h->stream);
     h->h_status.assign(B, 0);
@@ -412,13 +414,13 @@ static int create_handle(const mpopis_config* cfg, int as, int ss, mpopis_handle
     const int n0 = (cfg->policy == MPOPIS_POL_MPPI) ? h->as : cs;
     std::vector<double> eye((size_t)n0 * n0, 0.0);
     for (int i = 0; i < n0; ++i) eye[(size_t)i * n0 + i] = 1.0;
-    if (mpopis_set_Sigma(h, eye.data(), n0) != 0) { g_create_error = h->err; mpopis_destroy(h); return MPOPIS_ERR_HIP; }
-    if (mpopis_seed(h, cfg->seed) != 0) { g_create_error = h->err; mpopis_destroy(h); return MPOPIS_ERR_HIP; }
-    if (mpopis_reset(h) != 0) { g_create_error = h->err; mpopis_destroy(h); return MPOPIS_ERR_HIP; }
+    if (mpopis_set_Sigma(h, eye.data(), n0) != 0) return fail_create(h, MPOPIS_ERR_HIP, h->err);
+    if (mpopis_seed(h, cfg->seed) != 0) return fail_create(h, MPOPIS_ERR_HIP, h->err);
+    if (mpopis_reset(h) != 0) return fail_create(h, MPOPIS_ERR_HIP, h->err);
     if (cfg->policy == MPOPIS_POL_CMAMPPI) {
         h->init_cma_constants();
-        if ((long long)cs * h->m_elite < K) { g_create_error = "BoundsError: δs[order[ii]] needs cs*m_elite >= K (src/mppi_mpopi_policies.jl:593)"; mpopis_destroy(h); return MPOPIS_ERR_ARG; }
-        if (hipMemcpy(h->d_cma_ws, h->cma_ws_host.data(), sizeof(double) * K, hipMemcpyHostToDevice) != hipSuccess) { g_create_error = "upload failed"; mpopis_destroy(h); return MPOPIS_ERR_HIP; }
+        if ((long long)cs * h->m_elite < K) return fail_create(h, MPOPIS_ERR_ARG, "BoundsError: δs[order[ii]] needs cs*m_elite >= K (src/mppi_mpopi_policies.jl:593)");
+        if (hipMemcpy(h->d_cma_ws, h->cma_ws_host.data(), sizeof(double) * K, hipMemcpyHostToDevice) != hipSuccess) return fail_create(h, MPOPIS_ERR_HIP, "upload failed");
     }
     if (cfg->policy == MPOPIS_POL_CEMPPI) h->m_elite = (int)nearbyint(K * (1 - cfg->elite_threshold));   // :437
     // (no upper limit on K: beyond K = 8192 the sort is the chunked chip-wide rank sort, beyond 7168 the alias table is built on global arrays --
@@ -478,9 +480,7 @@ int mpopis_set_env_table(mpopis_handle* h, const double* data, int64_t n, int32_
     if (!h->custom.has_table) { h->err = "mpopis_set_env_table: the handle's code object has no mpopis_env_table_abi (build the env with MPOPIS_DEFINE_ENV_TABLE)"; return MPOPIS_ERR_ARG; }
     if (n < 0 || n > MPOPIS_ENV_MAX_TABLE) { h->err = "mpopis_set_env_table: n must be 0.." + std::to_string(MPOPIS_ENV_MAX_TABLE) + " doubles per slot"; return MPOPIS_ERR_ARG; }
     if (n > 0 && !data) { h->err = "mpopis_set_env_table: data is NULL with n > 0"; return MPOPIS_ERR_ARG; }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
+    if (const int rc = quiesce(h)) return rc;
     mpopis::CustomEnv& ce = h->custom;
     const size_t total = (size_t)n * (per_slot ? (size_t)h->B_full : 1);
     if (total > ce.table_cap) {
@@ -500,7 +500,7 @@ int mpopis_set_track(mpopis_handle* h, const double* x, const double* y, const d
     if (!h || !x || !y || !w || P < 2 || P > mpopis::kMaxTrackPoints) { if (h) h->err = "bad track (need 2 <= P <= 2048 points)"; return MPOPIS_ERR_ARG; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     double* d = nullptr;
-    if (dalloc(h, &d, (size_t)4 * P)) return MPOPIS_ERR_HIP;
+    if (h->shared_alloc(d, (size_t)4 * P)) return MPOPIS_ERR_HIP;
     std::vector<double> n2(P);
     for (int i = 0; i < P; ++i) n2[i] = x[i] * x[i] + y[i] * y[i];
     HIPCHK(h, hipMemcpyAsync(d + 3 * P, n2.data(), sizeof(double) * P, hipMemcpyHostToDevice, h->stream));
@@ -512,13 +512,13 @@ int mpopis_set_track(mpopis_handle* h, const double* x, const double* y, const d
     std::vector<double> nd; std::vector<int> ni;
     build_track_tables(P, x, y, nd, ni);
     double* dnd = nullptr; int* dni = nullptr;
-    if (dalloc(h, &dnd, nd.size()) || dalloc(h, &dni, ni.size())) return MPOPIS_ERR_HIP;
+    if (h->shared_alloc(dnd, nd.size()) || h->shared_alloc(dni, ni.size())) return MPOPIS_ERR_HIP;
     HIPCHK(h, hipMemcpyAsync(dnd, nd.data(), sizeof(double) * nd.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(dni, ni.data(), sizeof(int) * ni.size(), hipMemcpyHostToDevice, h->stream));
     std::vector<double> ring, cert;
     build_track_ring(P, x, y, w, n2.data(), nd, ring, cert);
     double* dring = nullptr;
-    if (dalloc(h, &dring, ring.size() + cert.size())) return MPOPIS_ERR_HIP;
+    if (h->shared_alloc(dring, ring.size() + cert.size())) return MPOPIS_ERR_HIP;
     HIPCHK(h, hipMemcpyAsync(dring, ring.data(), sizeof(double) * ring.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(dring + ring.size(), cert.data(), sizeof(double) * cert.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, wait_stream(h->stream));
@@ -617,22 +617,15 @@ static int set_Sigma0(mpopis_handle* h, const double* Sigma, int32_t n, bool per
             }
         else diag = false;
     }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (the set in force and the scratch are in use by whatever is still queued)
-    for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
+    if (const int rc = quiesce(h)) return rc;                  // (the set in force and the scratch are in use by whatever is still queued)
     mpopis_handle::Sigma0Set& dst = per_slot ? h->S0sl : h->S0sh;
-    if (!dst.Sigma) {                                           // first use of per-slot Σ: the slots' own buffers
-        double* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        const size_t want[5] = {(size_t)B * nn, (size_t)B * nn, (size_t)B * pd, nes ? (size_t)B * nn : 0, nes ? (size_t)B * nn : 0};
-        for (int i = 0; i < 5; ++i)
-            if (want[i] && hipMalloc((void**)&p[i], want[i] * sizeof(double)) != hipSuccess) {
-                (void)hipGetLastError();
-                for (int j = 0; j < i; ++j) if (p[j]) (void)hipFree(p[j]);
-                h->err = "mpopis_set_Sigma_slots: hipMalloc of the per-slot covariance buffers failed";
-                return MPOPIS_ERR_HIP;
-            }
-        for (double* q : p) if (q) h->allocs.push_back(q);
-        dst = {p[0], p[1], p[2], p[3], p[4]};
+    // per-slot Σ: the slots' own buffers, from the first such call on ([B] matrices each; S0 is their slot view, by S0stride / P0stride below).
+    // Whatever a failed call did allocate stays with the handle for the next one.
+    if (per_slot && (h->shared_alloc(dst.Sigma, B * nn) || h->shared_alloc(dst.L, B * nn) || (pd && h->shared_alloc(dst.Lp, B * pd)) ||
+                     (nes && (h->shared_alloc(dst.nesA, B * nn) || h->shared_alloc(dst.nesS, B * nn))))) {
+        (void)hipGetLastError();
+        h->err = "mpopis_set_Sigma_slots: hipMalloc of the per-slot covariance buffers failed";
+        return MPOPIS_ERR_HIP;
     }
     auto read_status = [&]() -> int {
         HIPCHK(h, hipMemcpyAsync(h->h_status.data(), h->d_status, sizeof(int) * M, hipMemcpyDeviceToHost, h->stream));
@@ -702,9 +695,7 @@ int mpopis_set_slot_hyper(mpopis_handle* h, const double* lambda, const double* 
     if (h->cfg.policy == MPOPIS_POL_NESMPPI && cma_sigma)
         for (int b = 0; b < B; ++b)
             if (!std::isfinite(cma_sigma[b])) { h->err = "nesmppi: step_factor (cma_sigma) must be finite (slot " + std::to_string(b) + ")"; return MPOPIS_ERR_ARG; }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (auto st : h->xstream) if (st) HIPCHK(h, hipStreamSynchronize(st));
+    if (const int rc = quiesce(h)) return rc;
     if (!lambda && !alpha && !lambda_ais && !cma_sigma) {       // back to the config's scalars
         h->sl_host.clear();
         h->d_sl_nil = h->d_sl_nil_ais = h->d_sl_gamma = h->d_sl_sigma = h->d_sl_nes_a = h->d_sl_nes_u = nullptr;
@@ -712,11 +703,9 @@ int mpopis_set_slot_hyper(mpopis_handle* h, const double* lambda, const double* 
         h->weights_in_moments = h->fold_weights_cfg;
         return MPOPIS_OK;
     }
-    if (!h->sl_buf) {
-        double* p = nullptr;
-        if (hipMalloc((void**)&p, sizeof(double) * 6 * B) != hipSuccess) { (void)hipGetLastError(); h->err = "mpopis_set_slot_hyper: hipMalloc of the per-slot value arrays failed"; return MPOPIS_ERR_HIP; }
-        h->allocs.push_back(p);
-        h->sl_buf = p;
+    if (!h->sl_buf) {                                           // six [B] arrays in one allocation; the pointers the kernels get are its slot views
+        if (h->shared_alloc(h->sl_buf, (size_t)6 * B)) { (void)hipGetLastError(); h->err = "mpopis_set_slot_hyper: hipMalloc of the per-slot value arrays failed"; return MPOPIS_ERR_HIP; }
+        for (double** v : {&h->d_sl_nil, &h->d_sl_nil_ais, &h->d_sl_gamma, &h->d_sl_sigma, &h->d_sl_nes_a, &h->d_sl_nes_u}) h->slot_view(*v, 1);
     }
     std::vector<double> host((size_t)4 * B), dev((size_t)6 * B);
     bool any_gamma = false;
@@ -733,7 +722,8 @@ int mpopis_set_slot_hyper(mpopis_handle* h, const double* lambda, const double* 
         dev[(size_t)4 * B + b] = -sg / ((double)K * K);
         dev[(size_t)5 * B + b] = sg / K;
     }
-    HIPCHK(h, hipMemcpy(h->sl_buf, dev.data(), sizeof(double) * 6 * B, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpyAsync(h->sl_buf, dev.data(), sizeof(double) * 6 * B, hipMemcpyHostToDevice, h->stream));      // (behind the buffer's zero-fill)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     h->sl_host.swap(host);
     h->d_sl_nil = h->sl_buf; h->d_sl_nil_ais = h->sl_buf + B; h->d_sl_gamma = h->sl_buf + 2 * (size_t)B; h->d_sl_sigma = h->sl_buf + 3 * (size_t)B;
     h->d_sl_nes_a = h->sl_buf + 4 * (size_t)B; h->d_sl_nes_u = h->sl_buf + 5 * (size_t)B;
@@ -792,7 +782,7 @@ int mpopis_get_Sigma(mpopis_handle* h, double* out) {
 int mpopis_rollout_costs(mpopis_handle* h, const double* x0, const double* U, const double* U_orig, const double* E,
                          const double* Sigma_inv, double* cost) {
     if (!h || !U || !E || !cost) return MPOPIS_ERR_ARG;
-    if (h->env.kind == MPOPIS_ENV_CAR && h->env.track.P == 0) { h->err = "track not set"; return MPOPIS_ERR_ARG; }
+    if (h->track_missing()) return MPOPIS_ERR_ARG;
     if (h->use_gvec() && !Sigma_inv) { h->err = "Sigma_inv required when alpha != 1"; return MPOPIS_ERR_ARG; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, K = h->K, cs = h->cs;
@@ -819,7 +809,7 @@ int mpopis_rollout_costs(mpopis_handle* h, const double* x0, const double* U, co
 
 int mpopis_env_step(mpopis_handle* h, const double* action, double* reward) {
     if (!h || !action) return MPOPIS_ERR_ARG;
-    if (h->env.kind == MPOPIS_ENV_CAR && h->env.track.P == 0) { h->err = "track not set"; return MPOPIS_ERR_ARG; }
+    if (h->track_missing()) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpyAsync(h->d_control, action, sizeof(double) * h->B * h->as, hipMemcpyHostToDevice, h->stream));
     fill_i32(h->d_status, 0, h->B, h->stream);
@@ -830,10 +820,10 @@ int mpopis_env_step(mpopis_handle* h, const double* action, double* reward) {
 
 int mpopis_env_query(mpopis_handle* h, double* reward, int32_t* within, double* dist, double* beta) {
     if (!h) return MPOPIS_ERR_ARG;
-    if (h->env.kind == MPOPIS_ENV_CAR && h->env.track.P == 0) { h->err = "track not set"; return MPOPIS_ERR_ARG; }
+    if (h->track_missing()) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, NC = std::max(1, h->env.ncars);
-    if (!h->d_qdist) { if (dalloc(h, &h->d_qdist, (size_t)B * NC) || dalloc(h, &h->d_qbeta, (size_t)B * NC) || dalloc(h, &h->d_qwithin, B)) return MPOPIS_ERR_HIP; }
+    if (h->slot_alloc(h->d_qdist, NC) || h->slot_alloc(h->d_qbeta, NC) || h->slot_alloc(h->d_qwithin, 1)) return MPOPIS_ERR_HIP;
     HIPCHK(h, launch_env_query(h->env, h->d_x, h->d_t, h->d_done, h->d_reward, h->d_qwithin, h->d_qdist, h->d_qbeta, B, h->stream));
     if (reward) HIPCHK(h, hipMemcpyAsync(reward, h->d_reward, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
     if (within) HIPCHK(h, hipMemcpyAsync(within, h->d_qwithin, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
@@ -855,16 +845,16 @@ int mpopis_get_trajectories(mpopis_handle* h, double* out) {
 int mpopis_policy_step(mpopis_handle* h, const mpopis_noise* noise, double* control, double* cost, double* weights,
                        double* E_out, int32_t* resample_idx0, int32_t* iters_run) {
     if (!h) return MPOPIS_ERR_ARG;
-    if (h->env.kind == MPOPIS_ENV_CAR && h->env.track.P == 0) { h->err = "track not set"; return MPOPIS_ERR_ARG; }
+    if (h->track_missing()) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, K = h->K, cs = h->cs, N = h->N;
     const size_t per = (size_t)cs * K;
     if (noise && noise->Z) {
-        if (!h->d_Zin) { if (dalloc(h, &h->d_Zin, (size_t)B * N * per)) return MPOPIS_ERR_HIP; }
+        if (h->slot_alloc(h->d_Zin, N * per)) return MPOPIS_ERR_HIP;
         HIPCHK(h, hipMemcpyAsync(h->d_Zin, noise->Z, sizeof(double) * B * N * per, hipMemcpyHostToDevice, h->stream));
         if (h->cfg.policy == MPOPIS_POL_PMCMPPI && N > 1) {
             if (!noise->res_i0 || !noise->res_u) { h->err = "pmcmppi with injected noise needs resampling draws"; return MPOPIS_ERR_ARG; }
-            if (!h->d_resi_in) { if (dalloc(h, &h->d_resi_in, (size_t)B * (N - 1) * K) || dalloc(h, &h->d_resu_in, (size_t)B * (N - 1) * K)) return MPOPIS_ERR_HIP; }
+            if (h->slot_alloc(h->d_resi_in, (size_t)(N - 1) * K) || h->slot_alloc(h->d_resu_in, (size_t)(N - 1) * K)) return MPOPIS_ERR_HIP;
             HIPCHK(h, hipMemcpyAsync(h->d_resi_in, noise->res_i0, sizeof(int32_t) * B * (N - 1) * K, hipMemcpyHostToDevice, h->stream));
             HIPCHK(h, hipMemcpyAsync(h->d_resu_in, noise->res_u, sizeof(double) * B * (N - 1) * K, hipMemcpyHostToDevice, h->stream));
         }
@@ -914,7 +904,7 @@ int mpopis_policy_call(mpopis_handle* h, const double* x, const int32_t* t, cons
         return rc;
     }
     if ((t || done) && !x) { h->err = "mpopis_policy_call: t / done without x"; return MPOPIS_ERR_ARG; }
-    if (h->env.kind == MPOPIS_ENV_CAR && h->env.track.P == 0) { h->err = "track not set"; return MPOPIS_ERR_ARG; }
+    if (h->track_missing()) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, K = h->K, cs = h->cs, as = h->as, ss = h->ss;
     const CallBox hb = call_box(h->h_call, B, ss, cs, as), db = call_box(h->d_call, B, ss, cs, as);
@@ -1021,7 +1011,7 @@ int mpopis_timing_read(mpopis_handle* h, char* names, int32_t names_cap, double*
 
 int mpopis_bench_policy_steps(mpopis_handle* h, int32_t steps, double* ms, double* rollouts) {
     if (!h || steps < 0) return MPOPIS_ERR_ARG;
-    if (h->env.kind == MPOPIS_ENV_CAR && h->env.track.P == 0) { h->err = "track not set"; return MPOPIS_ERR_ARG; }
+    if (h->track_missing()) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipEvent_t e0, e1;
     HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
@@ -1081,26 +1071,17 @@ void mpopis_handle::rollout(const double* Ucur, const double* Uorig, const doubl
 // calculate_trajectory_costs(pol, env) for the configured policy + functor tail.  `injected`: noise
 // staged in d_Zin / d_resi_in / d_resu_in, else device Philox streams (mpc_step, iteration).
 // Slot views: every per-slot buffer is laid out [B][...], so "slots [b0, b0 + nb)" is the same handle with its pointers moved.
+// The registry (slot_bufs: every slot_alloc / slot_view, with the extent it was declared with) does the moving; named here are only the views whose
+// stride changes at run time, each next to the variable that holds it.
 void mpopis_handle::shift_slots(ptrdiff_t db) {
-    const ptrdiff_t nn = (ptrdiff_t)cs * cs, per = (ptrdiff_t)cs * K;
+    for (const SlotBuf& sb : slot_bufs) {
+        char* q; memcpy(&q, sb.member, sizeof q);               // (the member is a T* of some T: read and written as bytes)
+        if (q) { q += db * (ptrdiff_t)sb.bytes_per_slot; memcpy(sb.member, &q, sizeof q); }
+    }
     auto mv = [db](auto*& p, ptrdiff_t stride) { if (p) p += db * stride; };
-    mv(d_x, ss); mv(d_xext, kMaxCars * kCarExt); mv(d_t, 1); mv(d_done, 1);
-    mv(d_U, cs); mv(d_Ucur, cs); mv(d_Uin, cs);
-    mv(d_Sig, nn); mv(d_L, nn); mv(d_tmpS, nn); mv(d_dscale, cs); mv(d_Lp, (ptrdiff_t)potrf_panel_doubles(cs));
-    mv(d_Z, per); mv(d_E, per); mv(d_Zin, (ptrdiff_t)N * per); mv(d_cost, K); mv(d_w, K); mv(d_wsum, 1); mv(d_cmin, 1);
-    mv(d_wn, cs); mv(d_mu, cs); mv(d_gvec, cs); mv(d_control, as); mv(d_reward, 1); mv(d_traj, (ptrdiff_t)K * T * ss);
-    mv(d_status, 1); mv(d_active, 1); mv(d_iters, 1); mv(d_iters_acc, 1); mv(d_seeds, 1);
-    mv(d_order, K); mv(d_resi, K); mv(d_alias, K); mv(d_residx_log, (ptrdiff_t)std::max(1, N - 1) * K); mv(d_resi_in, (ptrdiff_t)(N - 1) * K);
-    mv(d_resu, K); mv(d_accept, K); mv(d_alias_need, 1); mv(d_alias_stack, 2 * (ptrdiff_t)K); mv(d_resu_in, (ptrdiff_t)(N - 1) * K);
-    mv(d_part, (ptrdiff_t)(wcov_mfma_workspace_doubles(1, cs, ksplit)));
-    mv(d_cma_scal, 8); mv(d_cma_vec, 3 * (ptrdiff_t)cs); mv(d_sig2, 1);
-    mv(d_lanV, (ptrdiff_t)invsqrt_workspace_doubles(1, cs, lan_regions)); mv(d_lan_x, (ptrdiff_t)invsqrt_coop_words(1, cs)); mv(d_Cdw, cs); mv(d_fro_part, (cs + 15) / 16); mv(d_tri_dinv, (ptrdiff_t)trtri_dinv_doubles(1, cs)); mv(d_fro, 1); mv(d_lan_m, 1); mv(d_lan_prep, (ptrdiff_t)lanczos_prep_doubles(1)); mv(d_tri_cnt, 2);
-    mv(d_coop_flags, (ptrdiff_t)potrf_coop_flag_words(1, cs)); mv(d_potrf_redo, 1); mv(d_lan_redo, 1);
-    mv(d_nesS, nn); mv(d_nesA[0], nn); mv(d_nesA[1], nn); mv(d_nesM, nn); mv(d_nesg, cs); mv(d_nesC, 1); mv(d_nespart, (ptrdiff_t)nes_scatter_workspace_doubles(1, cs, ksplit));
-    mv(alive_gate, 1); mv(d_hs, kHarnessDoubles); mv(d_alive, 1); mv(d_actlog, actlog_stride);
     mv(S0.Sigma, (ptrdiff_t)S0stride); mv(S0.L, (ptrdiff_t)S0stride); mv(S0.Lp, (ptrdiff_t)P0stride); mv(S0.nesA, (ptrdiff_t)S0stride); mv(S0.nesS, (ptrdiff_t)S0stride);   // per-slot pol.Σ (stride 0: shared)
-    mv(d_sl_nil, 1); mv(d_sl_nil_ais, 1); mv(d_sl_gamma, 1); mv(d_sl_sigma, 1); mv(d_sl_nes_a, 1); mv(d_sl_nes_u, 1);          // per-slot λ, α, λ_ais, σ (null: the scalars)
     mv(custom.table_view, (ptrdiff_t)custom.table_stride);                     // a custom env's per-slot tables (stride 0: one shared table)
+    mv(d_actlog, actlog_stride);                                               // run_trials' action log of the current call
 }
 
 // pol(env) for all slots.  With >= 2 slots the batch may be split into parts that run as independent chains on

@@ -1,6 +1,7 @@
 // engine_handle.h -- the opaque handle behind include/mpopis.h (see engine.h for the HBM layout).
 #pragma once
 #include "engine.h"
+#include <algorithm>
 #include <functional>
 
 struct mpopis_handle {
@@ -26,7 +27,28 @@ struct mpopis_handle {
     mpopis::CustomEnv custom;              // MPOPIS_ENV_CUSTOM: the caller's code object (env.custom points here); unloaded in mpopis_destroy
     std::vector<double> custom_reset;      // ... and the state mpopis_reset restores (ss doubles)
     std::string err;
+    // Device memory the handle owns (freed in mpopis_destroy).  A per-slot buffer -- [B_full][per_slot] elements of T -- is declared ONCE, by the
+    // slot_alloc call that allocates it (the table in create_handle and the lazy sites beside their first use): that call is the record of its
+    // layout and what shift_slots moves it by.  shared_alloc: one buffer for the whole batch, never moved.  slot_view: a pointer into someone
+    // else's allocation that moves with the slots (null while unused).  All zero-filled on `stream`; a pointer already set is left alone, so
+    // a lazy site just calls them again.  The registry holds addresses of members: a handle is neither copied nor moved.
     std::vector<void*> allocs;
+    struct SlotBuf { void* member; size_t bytes_per_slot; };
+    std::vector<SlotBuf> slot_bufs;
+    int dev_alloc(void** p, size_t bytes);                     // engine_api.hip; sets err
+    template <class T> int shared_alloc(T*& p, size_t n) {
+        void* q = nullptr;
+        if (!p && dev_alloc(&q, std::max<size_t>(n, 1) * sizeof(T)) == 0) p = (T*)q;
+        return p ? MPOPIS_OK : MPOPIS_ERR_HIP;
+    }
+    template <class T> void slot_view(T*& p, size_t per_slot) { slot_bufs.push_back({&p, per_slot * sizeof(T)}); }
+    template <class T> int slot_alloc(T*& p, size_t per_slot, size_t pad = 0) {
+        if (p) return MPOPIS_OK;
+        if (shared_alloc(p, (size_t)B_full * per_slot + pad)) return MPOPIS_ERR_HIP;
+        slot_view(p, per_slot);
+        return MPOPIS_OK;
+    }
+    mpopis_handle() = default; mpopis_handle(const mpopis_handle&) = delete; mpopis_handle& operator=(const mpopis_handle&) = delete;
     // resident env + policy state
     double *d_x = nullptr, *d_xext = nullptr, *d_U = nullptr, *d_Ucur = nullptr, *d_Uin = nullptr;
     int *d_t = nullptr, *d_done = nullptr;
@@ -37,7 +59,7 @@ struct mpopis_handle {
     bool sigma_diag = false;                      // pol.Σ diagonal (per-slot Σ: in every slot); d_dscale then holds each slot's sqrt(diag)
     // pol.Σ, its factor, the factor's sampler panel and, for :nesmppi, A0 = sqrt(pol.Σ) and Σ0^-1.  S0 is the set IN FORCE: the shared buffers
     // (S0sh, stride 0) until the first mpopis_set_Sigma_slots, then the [B] copies (S0sl, allocated by that call; strides cs² and the panel size),
-    // moved with the slot views.  mpopis_set_Sigma switches back to the shared set.
+    // moved with the slot views by the strides below.  mpopis_set_Sigma switches back to the shared set.
     struct Sigma0Set { double *Sigma = nullptr, *L = nullptr, *Lp = nullptr, *nesA = nullptr, *nesS = nullptr; };
     Sigma0Set S0, S0sh, S0sl;
     size_t S0stride = 0, P0stride = 0;
@@ -96,7 +118,6 @@ struct mpopis_handle {
     double *d_qdist = nullptr, *d_qbeta = nullptr; int* d_qwithin = nullptr;
     // Level-3 harness
     double* d_hs = nullptr; int* d_alive = nullptr; const int* alive_gate = nullptr; bool status_sticky = false;
-    static constexpr int kHarnessDoubles = 16;                 // per-slot accumulator of the trial loop (engine_harness.hip, kH_N)
     double* d_actlog = nullptr; ptrdiff_t actlog_stride = 0;   // run_trials' action log of the current call ([B][num_steps + 1][as]) and its slot stride
     double noise_sx = 0.0, noise_sy = 0.0, noise_spsi = 0.0;   // simulate_car_racing state noise (car_example.jl:224-236)
     // RCCL communicator for the summary gather (engine_comm.hip); world == 1 needs none
@@ -146,6 +167,14 @@ struct mpopis_handle {
     void chains_join();
     int step_enqueue_view(bool injected, hipEvent_t wait_first, hipEvent_t record_after_first_sampler);
     void shift_slots(ptrdiff_t db);                           // move every per-slot device pointer by db slots (slot views)
+    // the checks and messages several entry points share
+    bool track_missing() { if (env.kind != MPOPIS_ENV_CAR || env.track.P != 0) return false; err = "track not set"; return true; }
+    int report_status(int st) {                               // the message that goes with the worst per-slot status of a call; returns st
+        if (st == MPOPIS_ERR_NOT_PD) err = "PosDefException: proposal covariance is not positive definite";
+        else if (st == MPOPIS_ERR_ACTION) err = "Action is not in action space (non-finite control/cost)";
+        else if (st == MPOPIS_ERR_NUMERIC) err = "cmamppi: Σ^-0.5 δw could not be formed (non-finite covariance, trace or δw)";
+        return st;
+    }
     int ais_update(int n, bool injected);
     int run_trials(int num_steps, int laps, double* records, double* actions);
     void init_cma_constants();

@@ -19,7 +19,6 @@ namespace mpopis {
 // per-slot accumulator (doubles): see kH_* indices
 enum { kH_rew = 0, kH_cnt, kH_lap, kH_prev_y, kH_trk, kH_beta, kH_crash, kH_vmean, kH_vmax, kH_bmean, kH_bmax,
        kH_lap0, kH_lap1, kH_lap2, kH_lap3, kH_rollouts, kH_N = 16 };
-static_assert(kH_N == mpopis_handle::kHarnessDoubles, "shift_slots moves d_hs by kHarnessDoubles per slot");
 
 __global__ void k_harness_init(double* hs, int* alive, int B) {
     const int b = blockIdx.x * 64 + threadIdx.x;
@@ -97,13 +96,10 @@ __global__ void k_zero_status(int* st, int B) { const int b = blockIdx.x * 64 + 
 }  // namespace mpopis
 
 int mpopis_handle::run_trials(int num_steps, int laps, double* records, double* actions) {
-    if (env.kind == MPOPIS_ENV_CAR && env.track.P == 0) { err = "track not set"; return MPOPIS_ERR_ARG; }
+    if (track_missing()) return MPOPIS_ERR_ARG;
     if (num_steps < 0 || laps < 0 || laps > 4) { err = "need num_steps >= 0 and 0 <= laps <= 4"; return MPOPIS_ERR_ARG; }
     if (hipSetDevice(cfg.device) != hipSuccess) { err = "hipSetDevice failed"; return MPOPIS_ERR_HIP; }
-    if (!d_hs) {
-        if (hipMalloc((void**)&d_hs, sizeof(double) * kH_N * B) != hipSuccess || hipMalloc((void**)&d_alive, sizeof(int) * B) != hipSuccess) { err = "hipMalloc failed"; return MPOPIS_ERR_HIP; }
-        allocs.push_back(d_hs); allocs.push_back(d_alive);
-    }
+    if (slot_alloc(d_hs, kH_N) || slot_alloc(d_alive, 1)) { err = "hipMalloc failed"; return MPOPIS_ERR_HIP; }
     // (d_actlog is a member for the length of this call: the part-chains log through their slot views of it)
     struct ActlogGuard { mpopis_handle* h; ~ActlogGuard() { if (h->d_actlog) (void)hipFree(h->d_actlog); h->d_actlog = nullptr; h->actlog_stride = 0; } } actlog_guard{this};
     if (actions) {
@@ -162,8 +158,5 @@ int mpopis_handle::run_trials(int num_steps, int laps, double* records, double* 
         r[9] = car && cnt > 0 ? h[kH_bmean] / cnt : 0.0; r[10] = car ? h[kH_bmax] : 0.0;
         r[11] = h[kH_beta]; r[12] = h[kH_trk]; r[13] = h[kH_crash]; r[14] = h[kH_rollouts]; r[15] = (double)worst;
     }
-    if (worst == MPOPIS_ERR_NOT_PD) err = "PosDefException: proposal covariance is not positive definite";
-    else if (worst == MPOPIS_ERR_ACTION) err = "Action is not in action space (non-finite control/cost)";
-    else if (worst == MPOPIS_ERR_NUMERIC) err = "cmamppi: Σ^-0.5 δw could not be formed (non-finite covariance, trace or δw)";
-    return worst;
+    return report_status(worst);
 }
