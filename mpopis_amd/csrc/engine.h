@@ -202,6 +202,12 @@ size_t potrf_coop_flag_words(int B, int n);
 // panel (nullable, n <= kPanelRows): second copy of the factor in the staging layout of the fused sampler (potrf_panel_doubles(n) per slot)
 constexpr int kPanelRows = 128;
 size_t potrf_panel_doubles(int n);
+// The kernel launch_potrf picks, as a pure function of the launch's shape (the launcher switches on it; tools/kbench_dense.hip writes it into its
+// result so that a test written for one form fails when a threshold moves).  G, S, coop_lds: cooperative form only (workgroups per matrix, panels
+// per ownership block, dynamic LDS of one workgroup).  MPOPIS_POTRF_REG / _G / _S and MPOPIS_COOP_MAX_WG are read once per process.
+enum PotrfKernel { POTRF_LDS = 0, POTRF_REG = 1, POTRF_COOP = 2 /* followed by the one-workgroup kernel on the slots marked in redo */, POTRF_GLOBAL = 3 };
+struct PotrfForm { PotrfKernel kernel = POTRF_GLOBAL; int G = 0, S = 0; size_t coop_lds = 0; };
+PotrfForm potrf_form(int B, int n, bool coop_usable, int share = 1);
 void launch_potrf(const double* A, size_t Astride, double* L, int B, int n, const double* scale, int* status, int* active, hipStream_t s,
                   const CoopCtx& coop = CoopCtx(), double* panel = nullptr, size_t pstride = 0);
 void launch_chol_solve_gvec(const double* L, size_t Lstride, const double* Uorig, SlotVal gamma, double* g, int B, int n, const int* active, hipStream_t s,

@@ -791,23 +791,58 @@ void launch_lanczos_invsqrt(const double* A, const double* prep, const double* b
 // :nesmppi's A = sqrt(Σ) of a dense pol.Σ (src/mppi_mpopi_policies.jl:849, LinearAlgebra's sqrt of a symmetric matrix: eigen-based): the Jacobi
 // iteration above on ONE workgroup, then A = V diag(λ^½) V', lower triangle computed and mirrored.  A non-positive eigenvalue is MPOPIS_ERR_NOT_PD
 // (the reference's MvNormal(Σ) would throw PosDefException).  Once per mpopis_set_Sigma; M, V: n x n global scratch.
-__global__ void __launch_bounds__(kLanThreads) k_sym_sqrt(const double* __restrict__ A, double* M, double* V, double* __restrict__ out, int* status, int n) {
+// Every column of V passes through ~10 sweeps x (n - 1) rotations whose roundings add up like a random walk: ||V'V - I||_F ~ n sqrt(10 n) u (1.5e-12 at
+// n = 300) and the diagonal of M drifts likewise, so V diag V' straight from the iteration is ~60 x less accurate than LAPACK's eigen route (6.9e-13 against
+// 1.2e-14 in the Frobenius norm at n = 300).  One Newton-Schulz step V <- V (3 I - V'V) / 2 restores orthogonality to second order and Rayleigh quotients
+// against the INPUT replace the drifted diagonal (then 1.7e-14); four n^3 products by one workgroup on a path that runs once per mpopis_set_Sigma.
+__global__ void __launch_bounds__(kLanThreads) k_sym_sqrt(const double* __restrict__ A, double* M, double* V, double* out, int* status, int n) {
     extern __shared__ __attribute__((aligned(16))) double sh_sq[];
     jacobi_eig_slot(A, M, V, n, sh_sq);
     __syncthreads();
     double* ev = sh_sq;                    // [n] (the rotation scratch is free now)
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int bad = 0;
-    for (int j = threadIdx.x; j < n; j += kLanThreads) { const double l = M[j + (size_t)j * n]; if (!(l > 0.0)) bad = 1; ev[j] = l > 0.0 ? sqrt(l) : 0.0; }
+    for (int j = tid; j < n; j += kLanThreads) { const double l = M[j + (size_t)j * n]; if (!(l > 0.0)) bad = 1; ev[j] = l; }
     bad = __syncthreads_or(bad);
-    if (bad) { if (threadIdx.x == 0) status_raise(status, MPOPIS_ERR_NOT_PD); return; }
-    for (int e = threadIdx.x; e < n * n; e += kLanThreads) {
+    if (bad) { if (tid == 0) status_raise(status, MPOPIS_ERR_NOT_PD); return; }
+    for (int e = tid; e < n * n; e += kLanThreads) {              // M <- G = V'V (the diagonal of M is in ev)
+        const int i = e % n, j = e / n;
+        double s = 0.0;
+        for (int k = 0; k < n; ++k) s = fma(V[k + (size_t)i * n], V[k + (size_t)j * n], s);
+        M[e] = s;
+    }
+    __syncthreads();
+    for (int e = tid; e < n * n; e += kLanThreads) {              // out <- V2 = V (3 I - G) / 2
+        const int i = e % n, j = e / n;
+        double s = 0.0;
+        for (int k = 0; k < n; ++k) s = fma(V[i + (size_t)k * n], M[k + (size_t)j * n], s);
+        out[e] = fma(-0.5, s, 1.5 * V[e]);
+    }
+    __syncthreads();
+    for (int e = tid; e < n * n; e += kLanThreads) {              // M <- A V2
+        const int i = e % n, j = e / n;
+        double s = 0.0;
+        for (int k = 0; k < n; ++k) s = fma(A[i + (size_t)k * n], out[k + (size_t)j * n], s);
+        M[e] = s;
+    }
+    __syncthreads();
+    for (int j = wv; j < n; j += kLanWaves) {                     // λ_j = v_j' A v_j / v_j' v_j: one wave per column (the iteration's own value if that is not positive)
+        double num = 0.0, den = 0.0;
+        for (int i = lane; i < n; i += 64) { const double v = out[i + (size_t)j * n]; num = fma(v, M[i + (size_t)j * n], num); den = fma(v, v, den); }
+        num = wave_sum(num); den = wave_sum(den);
+        if (lane == 0) { const double rq = num / den; ev[j] = sqrt(rq > 0.0 ? rq : ev[j]); }
+    }
+    __syncthreads();
+    for (int e = tid; e < n * n; e += kLanThreads) {              // V <- V2 diag(λ^½) V2', lower triangle computed and mirrored
         const int i = e % n, j = e / n;
         if (i < j) continue;
         double s = 0.0;
-        for (int m = 0; m < n; ++m) s = fma(V[i + (size_t)m * n] * ev[m], V[j + (size_t)m * n], s);
-        out[i + (size_t)j * n] = s;
-        out[j + (size_t)i * n] = s;
+        for (int m = 0; m < n; ++m) s = fma(out[i + (size_t)m * n] * ev[m], out[j + (size_t)m * n], s);
+        V[i + (size_t)j * n] = s;
+        V[j + (size_t)i * n] = s;
     }
+    __syncthreads();
+    for (int e = tid; e < n * n; e += kLanThreads) out[e] = V[e];
 }
 void launch_sym_sqrt(const double* A, double* M, double* V, double* out, int* status, int n, hipStream_t s) {
     const size_t lds = (size_t)(3 * ((n + 1) / 2) + 2 + 2 * kLanWaves + n + 8) * sizeof(double);

@@ -716,26 +716,17 @@ int coop_test_drop() {
 
 size_t potrf_panel_doubles(int n) { return n <= kPanelRows ? (size_t)((n + 15) / 16) * 16 * kPanelRows : 0; }
 
-void launch_potrf(const double* A, size_t Astride, double* L, int B, int n, const double* scale, int* status, int* active, hipStream_t s,
-                  const CoopCtx& coop, double* panel, size_t pstride) {
+// Which kernel launch_potrf runs, as a function of the launch's shape alone (the environment knobs are read once per process, the device's LDS and
+// CU count once per ordinal).  coop_usable: the caller's CoopCtx has its workspace; share: CoopCtx::share.
+PotrfForm potrf_form(int B, int n, bool coop_usable, int share) {
+    PotrfForm f;
     const int npad = (n + kNB - 1) / kNB * kNB, npan = npad / kNB;
     const size_t bytes = (size_t)npad * npad * sizeof(double);
-    if (bytes <= 150 * 1024) {
-        static std::atomic<unsigned long long> seen{0};
-        ensure_dyn_lds((const void*)k_potrf_lds, 150 * 1024, seen);
-        hipLaunchKernelGGL(k_potrf_lds, dim3(B), dim3(512), bytes, s, A, Astride, L, n, npad, scale, status, active, n <= kPanelRows ? panel : nullptr, pstride);
-        return;
-    }
+    if (bytes <= 150 * 1024) { f.kernel = POTRF_LDS; return f; }
     static const int env_reg = [] { const char* e = getenv("MPOPIS_POTRF_REG"); return e ? atoi(e) : 1; }();      // tests / A-B: 0 = the cluster and global kernels only
     // n = 241 .. 304: the register-resident kernel (n = 300: 133 us at one slot, 140 us at 64 -- clusters 160, one-workgroup global 225; below 16 panels
     // its fixed costs -- 8 us of loads through one CU, ~5 us per panel whatever its height -- lose to the clusters: n = 240: 123 vs 120, n = 144: 84 vs 68)
-    if (env_reg && npan >= kRegMinPan && npan <= kRegMaxPan && potrf_reg_fits_device()) {
-        static std::atomic<unsigned long long> seenr{0};
-        const size_t rbytes = potrf_reg_lds_bytes(n);
-        ensure_dyn_lds((const void*)k_potrf_reg, (int)potrf_reg_lds_bytes(kRegMaxPan * kNB), seenr);
-        hipLaunchKernelGGL(k_potrf_reg, dim3(B), dim3(64 * kRegWaves), rbytes, s, A, Astride, L, n, scale, status, active);
-        return;
-    }
+    if (env_reg && npan >= kRegMinPan && npan <= kRegMaxPan && potrf_reg_fits_device()) { f.kernel = POTRF_REG; return f; }
     static const int env_G = [] { const char* e = getenv("MPOPIS_POTRF_G"); return e ? atoi(e) : -1; }();
     static const int env_S = [] { const char* e = getenv("MPOPIS_POTRF_S"); return e ? atoi(e) : -1; }();
     // panels per ownership block.  S = 2 halves the hand-offs on the critical path but measured no faster (162 vs 158 us at n = 300): the
@@ -746,7 +737,7 @@ void launch_potrf(const double* A, size_t Astride, double* L, int B, int n, cons
     if (G > nblk) G = nblk;
     size_t coop_lds = 0;
     int nown0 = 0;
-    if (G >= 2 && coop.usable()) {
+    if (G >= 2 && coop_usable) {
         size_t own = 0;                                           // workgroup 0 owns the tallest panels
         for (int q = 0;; ++q) {
             const int c = (q / S) * S * G + (q % S);
@@ -759,14 +750,40 @@ void launch_potrf(const double* A, size_t Astride, double* L, int B, int n, cons
     // clusters should be co-resident: one workgroup per CU (LDS), the grid at most the device's CU count.  Not assumed: kernels of other
     // streams / processes may hold CUs, so a cluster that gives up (bounded waits) marks its slot in coop.redo and the one-workgroup kernel
     // queued right behind recomputes exactly those slots (A is not modified).
+    if (coop_lds && coop_lds <= 150 * 1024 && nown0 <= kCoopMaxOwn && B * G * share <= coop_max_workgroups()) {
+        f.kernel = POTRF_COOP; f.G = G; f.S = S; f.coop_lds = coop_lds;
+        return f;
+    }
+    f.kernel = POTRF_GLOBAL;
+    return f;
+}
+
+void launch_potrf(const double* A, size_t Astride, double* L, int B, int n, const double* scale, int* status, int* active, hipStream_t s,
+                  const CoopCtx& coop, double* panel, size_t pstride) {
+    const int npad = (n + kNB - 1) / kNB * kNB;
+    const PotrfForm f = potrf_form(B, n, coop.usable(), coop.share);
+    if (f.kernel == POTRF_LDS) {
+        const size_t bytes = (size_t)npad * npad * sizeof(double);
+        static std::atomic<unsigned long long> seen{0};
+        ensure_dyn_lds((const void*)k_potrf_lds, 150 * 1024, seen);
+        hipLaunchKernelGGL(k_potrf_lds, dim3(B), dim3(512), bytes, s, A, Astride, L, n, npad, scale, status, active, n <= kPanelRows ? panel : nullptr, pstride);
+        return;
+    }
+    if (f.kernel == POTRF_REG) {
+        static std::atomic<unsigned long long> seenr{0};
+        const size_t rbytes = potrf_reg_lds_bytes(n);
+        ensure_dyn_lds((const void*)k_potrf_reg, (int)potrf_reg_lds_bytes(kRegMaxPan * kNB), seenr);
+        hipLaunchKernelGGL(k_potrf_reg, dim3(B), dim3(64 * kRegWaves), rbytes, s, A, Astride, L, n, scale, status, active);
+        return;
+    }
     const size_t strip = (size_t)n * (kNB + 1) * sizeof(double);                             // panel strip
     static std::atomic<unsigned long long> seen2{0};
     ensure_dyn_lds((const void*)k_potrf_global, 150 * 1024, seen2);
-    if (coop_lds && coop_lds <= 150 * 1024 && nown0 <= kCoopMaxOwn && B * G * coop.share <= coop_max_workgroups()) {
+    if (f.kernel == POTRF_COOP) {
         static std::atomic<unsigned long long> seen3{0};
         ensure_dyn_lds((const void*)k_potrf_coop, 150 * 1024, seen3);
         const unsigned long long epoch = ++*coop.epoch;
-        hipLaunchKernelGGL(k_potrf_coop, dim3(B * G), dim3(kCoopThreads), coop_lds, s, A, Astride, L, n, G, S, scale, status, active, coop.flags, epoch,
+        hipLaunchKernelGGL(k_potrf_coop, dim3(B * f.G), dim3(kCoopThreads), f.coop_lds, s, A, Astride, L, n, f.G, f.S, scale, status, active, coop.flags, epoch,
                            coop.redo, coop.timeouts, coop_wait_ticks(), coop_test_drop());
         hipLaunchKernelGGL(k_potrf_global, dim3(B), dim3(1024), strip, s, A, Astride, L, n, scale, status, active, coop.redo);
         return;
