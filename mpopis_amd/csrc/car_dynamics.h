@@ -92,13 +92,15 @@ struct Track {           // env.track.{x′,y′,lane_width′} (+ n2[i] = x′[
     // row i = the nbrw points closest to q_i in ascending distance (rank 0 = i itself), row stride nbrw + 1
     const int* nbr_idx; const double* nbr_dist; int nbrw;
     // optional ring table for the straight-line fast paths of the rollout kernels (nullptr => within_track only): entry e, -kRingPad <= e <= P-1+kRingPad,
-    // at ring[4 (e + kRingPad) .. +3] = {x, y, |q|^2, lane_width} of track point e mod P -- the ring neighbours of any point are then at
-    // fixed offsets (no wrap-around index arithmetic); ring_cert[i] = ring_r2[i], ring_cert[P + i] = ring5_r2[i] (see below)
+    // at ring[kRingStride (e + kRingPad) .. +5] = {x, y, |q|^2, lane_width, tx, ty} of track point i = e mod P, (tx, ty) = the unit vector from
+    // q_i to its ring successor q_(i+1) -- the ring neighbours of any point are then at fixed offsets (no wrap-around index arithmetic) and the
+    // distance to a track segment is one cross product (track_line_dist); ring_cert[i] = ring_r2[i], ring_cert[P + i] = ring5_r2[i] (see below)
     const double* ring = nullptr; const double* ring_cert = nullptr;
 };
 constexpr int kRingPad = 3;          // a nearest point up to two ring steps from the anchor, plus its own ring neighbours
+constexpr int kRingStride = 6;       // doubles per ring-table entry
 constexpr int kTrackNbrW = 16;
-constexpr int kMaxTrackPoints = 2048;   // mpopis_set_track's limit (the rollout kernels stage 48 B per point in LDS)
+constexpr int kMaxTrackPoints = 2048;   // mpopis_set_track's limit (the rollout kernels stage 64 B per point in LDS: a 48-B ring entry and two certificates)
 // Row i of nbr_dist has one spare slot (index nbrw): it holds ring_r2[i] = (1 - 1e-9) x the squared distance from q_i to the nearest
 // track point that is NOT one of its ring neighbours {i-1, i, i+1} (+inf when there is none).  If a position p satisfies
 // 4 |p - q_i|^2 < ring_r2[i], every non-ring point j is farther from p than q_i is (|p - q_j| >= |q_j - q_i| - |p - q_i| > |p - q_i|),
@@ -112,6 +114,17 @@ constexpr int kMaxTrackPoints = 2048;   // mpopis_set_track's limit (the rollout
 #include <utility>
 #include <vector>
 namespace mpopis {
+// unit vector from track point (x0, y0) to its ring successor (x1, y1): once per point for the ring table, or on the spot for a Track without
+// one.  Host: IEEE sqrt and division in long double, rounded once, so each component is within 0.5 ulp (+ 2^-63) -- track_line_dist's error bound
+// leans on that.  (Coincident points give NaN, hence a NaN distance -- as the literal projection's 0 / 0 does.)
+MP_HD void track_tangent(double x0, double y0, double x1, double y1, double* tx, double* ty) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double vx = x1 - x0, vy = y1 - y0, n = sqrt(fma(vx, vx, vy * vy));            // (device callers always have the table; kept for completeness)
+#else
+    const long double vx = (long double)x1 - x0, vy = (long double)y1 - y0, n = sqrtl(vx * vx + vy * vy);
+#endif
+    *tx = (double)(vx / n); *ty = (double)(vy / n);
+}
 // host: ring table (see Track::ring) and certification radii from the neighbour table
 inline void build_track_ring(int P, const double* x, const double* y, const double* w, const double* n2, const std::vector<double>& nd, std::vector<double>& ring, std::vector<double>& cert);
 // host: neighbour tables of the anchored nearest-point search (row stride W + 1, see Track) for P points; W = min(kTrackNbrW, P)
@@ -144,11 +157,12 @@ inline double ring_cert_radius2(int P, const double* x, const double* y, int i, 
 // see bit-identical distances, or a near-tie could resolve differently depending on the path a wave took)
 inline void build_track_ring(int P, const double* x, const double* y, const double* w, const double* n2, const std::vector<double>& nd, std::vector<double>& ring, std::vector<double>& cert) {
     const int W = std::min<int>(kTrackNbrW, P), S = W + 1;
-    ring.assign((size_t)(P + 2 * kRingPad) * 4, 0.0); cert.assign((size_t)2 * P, 0.0);
+    ring.assign((size_t)(P + 2 * kRingPad) * kRingStride, 0.0); cert.assign((size_t)2 * P, 0.0);
     for (int e = -kRingPad; e < P + kRingPad; ++e) {
-        const int i = ((e % P) + P) % P;
-        double* o = ring.data() + (size_t)(e + kRingPad) * 4;
+        const int i = ((e % P) + P) % P, ip = (i == P - 1) ? 0 : i + 1;
+        double* o = ring.data() + (size_t)(e + kRingPad) * kRingStride;
         o[0] = x[i]; o[1] = y[i]; o[2] = n2[i]; o[3] = w[i];
+        track_tangent(x[i], y[i], x[ip], y[ip], &o[4], &o[5]);
     }
     for (int i = 0; i < P; ++i) { cert[i] = nd[(size_t)i * S + W]; cert[P + i] = ring_cert_radius2(P, x, y, i, 2); }
 }
@@ -264,6 +278,28 @@ MP_HD double fast_sqrt(double v) {
 #endif
 }
 
+// fast_sqrt that also hands back 1 / sqrt(v): the coupled iteration's h converges to 1 / (2 sqrt v) alongside g, so 2h is a reciprocal of the
+// square root good to ~20 ulp for free; one residual correction against the RETURNED root s (e = 1 - s 2h, exact in the fma, then 2h + 2h e)
+// leaves e^2 ~ 1e-29 plus the final rounding: max 0.500 ulp of 1 / s over fy_max in [1e-4, 1e5], the same as fast_rcp(s) (both measured,
+// tools/rcp_acc.hip) -- for 3 VALU ops instead of v_rcp_f64 + 4.  s has the same bits as fast_sqrt(v).  Host: sqrt and a division.
+MP_HD double fast_sqrt_rsq(double v, double* rs) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    v += 1e-300;
+    const double y = __builtin_amdgcn_rsq(v);
+    double g = v * y, h = 0.5 * y;
+    const double r = fma(-h, g, 0.5);
+    g = fma(g, r, g); h = fma(h, r, h);
+    const double s = fma(fma(-g, g, v), h, g);
+    const double y2 = h + h;
+    *rs = fma(fma(-s, y2, 1.0), y2, y2);
+    return s;
+#else
+    const double s = sqrt(v);
+    *rs = 1.0 / s;
+    return s;
+#endif
+}
+
 // max(min(v, thr), -thr) (v_min_f64 + v_max_f64 with a negated source, no input canonicalisation; callers
 // guarantee non-NaN arguments)
 MP_HD double clamp_sym(double v, double thr) {
@@ -291,20 +327,20 @@ MP_HD double fma_v(double a, double b, double c) {
 
 struct TireK { double fymax, thr, k2, k3; };
 
-// fy_max of an axle (:253) and, from it, the rest of the brush-model constants.  Two functions because the general sub-step only needs fy_max
-// while the tyre saturates (the usual state of a car that is not moving forward) -- the other three are functions of fy_max alone, so deriving them
-// on demand gives the same bits as deriving them up front.
-MP_HD double tire_fymax(double mufz, double fxt) { return fast_sqrt(fmax(fma(mufz, mufz, -(fxt * fxt)), 1e-8)); }   // mufz = μ f_z
-MP_HD TireK tire_from_fymax(double fymax, double Ca) {
+// fy_max of an axle (:253) with its reciprocal rf (a by-product of the square root, fast_sqrt_rsq) and, from the two, the rest of the brush-model
+// constants.  Two functions because the general sub-step only needs fy_max while the tyre saturates (the usual state of a car that is not moving
+// forward) -- the other three are functions of (fy_max, rf) alone, so deriving them on demand gives the same bits as deriving them up front.
+MP_HD double tire_fymax(double mufz, double fxt, double* rf) { return fast_sqrt_rsq(fmax(fma(mufz, mufz, -(fxt * fxt)), 1e-8), rf); }   // mufz = μ f_z
+MP_HD TireK tire_from_fymax(double fymax, double rf, double Ca) {
     TireK k;
     k.fymax = fymax;
-    const double rf = fast_rcp(k.fymax), rc = 1.0 / Ca;        // rc: Ca is wave-uniform
+    const double rc = 1.0 / Ca;                                // rc: Ca is wave-uniform
     k.thr = 3 * k.fymax * rc;                                  // tan of the switch angle :255
     k.k2 = ((Ca * Ca) * (1.0 / 3.0)) * rf;                     // C^2/(3 fy_max)
     k.k3 = ((Ca * Ca * Ca) * (1.0 / 27.0)) * (rf * rf);        // C^3/(27 fy_max^2)
     return k;
 }
-MP_HD TireK tire_consts(double mufz, double Ca, double fxt) { return tire_from_fymax(tire_fymax(mufz, fxt), Ca); }
+MP_HD TireK tire_consts(double mufz, double Ca, double fxt) { double rf; const double fymax = tire_fymax(mufz, fxt, &rf); return tire_from_fymax(fymax, rf, Ca); }
 
 // Car state as the kernels carry it: the reference's 8 doubles plus sin/cos of psi and delta, which
 // are advanced by angle addition and never re-evaluated inside a rollout.
@@ -344,14 +380,14 @@ MP_HD double tire_poly(double ta, double Ca, const TireK& k) {
 
 // What the general sub-step needs of an action's forces for ONE value of sign(Vx) (:310-318): the axle drive / brake forces and the two fy_max.
 // They depend on (pedal, sign Vx) only, so a rollout kernel derives them once per action and sign instead of once per sub-step (2 square roots).
-struct AxleForces { double fxf, fxr, fymf, fymr; };
+struct AxleForces { double fxf, fxr, fymf, fymr, rff, rfr; };   // rff, rfr = 1 / fy_max of the two axles (tire_fymax)
 MP_HD AxleForces car_axle_forces(const CarParams& p, double pedal, double sg) {
     AxleForces a;
     const double fx = fma(p.Fxmax, fmax(pedal, 0.0), fma(p.Fxmin * fmin(pedal, 0.0), sg, pedal * 0.0));     // :310-312 (pedal * 0.0: a NaN pedal propagates, see car_action_consts)
     const double lam = (pedal <= 0) ? p.lbrake : p.ldrive;
     a.fxf = lam * fx; a.fxr = (1 - lam) * fx;
-    a.fymf = tire_fymax(fma(-p.mfz_f1, fx, p.mfz_f0), a.fxf);                                // :262-272 (same derived constants as the hot path)
-    a.fymr = tire_fymax(fma(p.mfz_r1, fx, p.mfz_r0), a.fxr);
+    a.fymf = tire_fymax(fma(-p.mfz_f1, fx, p.mfz_f0), a.fxf, &a.rff);                              // :262-272 (same derived constants as the hot path)
+    a.fymr = tire_fymax(fma(p.mfz_r1, fx, p.mfz_r0), a.fxr, &a.rfr);
     return a;
 }
 
@@ -442,14 +478,14 @@ MP_HD void car_substep(const CarParams& p, const ActionConsts& k, double sd, dou
         const double fx_aero = (Vx > 0.0) ? f_drag : ((Vx < 0.0) ? -f_drag : f_drag * sg);
         fyr = (Vx == 0.0 && yr == 0.0) ? 0.0 : ((yr >= 0.0) ? -a.fymr : a.fymr);
         if (Vx > 0.0) {
-            const TireK kr = tire_from_fymax(a.fymr, p.Car);
+            const TireK kr = tire_from_fymax(a.fymr, a.rfr, p.Car);
             const double ta = yr / Vx;
             if (fabs(ta) < kr.thr) fyr = tire_poly(ta, p.Car, kr);
         }
         if (Vx == 0.0 && yf == 0.0) { xq = cd; yq = -sd; }     // atan2(0,0) = 0 -> alpha_f = -delta
         double fyf = ((xq > 0.0 ? yq : yf) >= 0.0) ? -a.fymf : a.fymf;
         if (xq > 0.0) {
-            const TireK kf = tire_from_fymax(a.fymf, p.Caf);
+            const TireK kf = tire_from_fymax(a.fymf, a.rff, p.Caf);
             const double ta = yq / xq;
             if (fabs(ta) < kf.thr) fyf = tire_poly(ta, p.Caf, kf);
         }
@@ -536,22 +572,33 @@ MP_HD void car_action_step(const CarParams& p, CarState& c, double a0, double a1
 }
 
 // Tail of within_track (car_racing_tracks.jl:75-90): nearest point p1 with its ring predecessor pm / successor pp -> distance of p from the
-// line through p1 and the nearer of the two, and the lane test.  Shared by the general search and the ring fast path (identical arithmetic,
-// so a rollout's cost does not depend on which of the two found the nearest point).
-MP_HD bool track_project(double px, double py, double p1x, double p1y, double pmx, double pmy, double ppx, double ppy, double lane_w, double* dist_out) {
+// line through p1 and the nearer of the two, and the lane test.  The reference projects p onto that line (t = u.v / |v|^2, foot point, |e|); the
+// distance of a point from a line is |u x t^| with t^ the line's unit tangent, which is a constant of the track: tabulated in the ring table
+// (tests/test_track_projection_cpu.py: within 2.2 ulp x |u| of a long-double distance on every bundled track).  Two steps, shared by every path: track_prev_nearer
+// chooses the neighbour, track_line_dist measures against the chosen segment's tangent (the sign of t^ is irrelevant).
+MP_HD bool track_prev_nearer(double px, double py, double pmx, double pmy, double ppx, double ppy) {
     const double ax = pmx - px, ay = pmy - py, bx = ppx - px, by = ppy - py;
     // :77-79 `dist(prev) <= dist(next)` decided on the squared distances (sqrt is monotone).  Only when the two squares
     // differ by an ulp or two could the rounding of the reference's square roots turn `>` into its tie (-> prev); at that
     // point the position is equidistant from both neighbours to 1e-16 and the reference's own choice is rounding noise.
     const double dm2 = fma(ax, ax, ay * ay), dp2 = fma(bx, bx, by * by);
-    const bool prev = dm2 <= dp2;
-    const double p2x = prev ? pmx : ppx, p2y = prev ? pmy : ppy;
-    const double ux = px - p1x, uy = py - p1y, vx = p2x - p1x, vy = p2y - p1y;
-    const double t = fma(ux, vx, uy * vy) * fast_rcp(fma(vx, vx, vy * vy));    // :87
-    const double ex = fma(t, vx, p1x) - px, ey = fma(t, vy, p1y) - py;         // :88-89
-    const double dist = fast_sqrt(fma(ex, ex, ey * ey));
+    return dm2 <= dp2;
+}
+MP_HD bool track_line_dist(double px, double py, double p1x, double p1y, double tx, double ty, double lane_w, double* dist_out) {
+    const double ux = px - p1x, uy = py - p1y;
+    // :87-89 as a cross product.  Error: u and t^ carry 1 and 0.5 ulp per component, the product and the fma one rounding each:
+    // |dist - exact| <= 3.5 ulp x |u| |t^| (first order), i.e. 6e-15 m at the lane edge (15 m)
+    const double dist = fabs(fma(ux, ty, -(uy * tx)));
     *dist_out = dist;
     return dist < lane_w;                                                      // :90
+}
+// The tail for a handle with a ring table, the ONE place every path of such a handle ends in (ring tiers and general search alike: identical
+// arithmetic on identical operands, so a rollout's cost does not depend on which of them found the nearest point): e = the nearest point's ring
+// entry.  The segment to the successor has the entry's own tangent, the one to the predecessor the predecessor's.
+MP_HD bool ring_entry_project(const double* e, double px, double py, double* dist_out) {
+    const bool prev = track_prev_nearer(px, py, e[-kRingStride], e[-kRingStride + 1], e[kRingStride], e[kRingStride + 1]);
+    const double* te = prev ? e - kRingStride : e;
+    return track_line_dist(px, py, e[0], e[1], te[4], te[5], e[3], dist_out);
 }
 
 // within_track(track, pos): car_racing_tracks.jl:68-92.
@@ -617,12 +664,17 @@ MP_HD bool within_track_m2(const Track& tk, double px, double py, double m2x, do
         }
     }
     if (anchor) *anchor = mi;
+    if (tk.ring) return ring_entry_project(tk.ring + (size_t)kRingStride * (mi + kRingPad), px, py, dist_out);
+    // no ring table (host-only callers): the same two steps, the chosen segment's tangent derived on the spot by the table's own arithmetic
     if (!have_pts) {
         const int im = (mi == 0) ? tk.P - 1 : mi - 1;                          // mod1 :75-76
         const int ip = (mi == tk.P - 1) ? 0 : mi + 1;
         p1x = tk.x[mi]; p1y = tk.y[mi]; pmx = tk.x[im]; pmy = tk.y[im]; ppx = tk.x[ip]; ppy = tk.y[ip];
     }
-    return track_project(px, py, p1x, p1y, pmx, pmy, ppx, ppy, tk.w[mi], dist_out);
+    double tx, ty;
+    if (track_prev_nearer(px, py, pmx, pmy, ppx, ppy)) track_tangent(pmx, pmy, p1x, p1y, &tx, &ty);
+    else track_tangent(p1x, p1y, ppx, ppy, &tx, &ty);
+    return track_line_dist(px, py, p1x, p1y, tx, ty, tk.w[mi], dist_out);
 }
 
 MP_HD bool within_track(const Track& tk, double px, double py, double* dist_out, int* anchor) {
@@ -634,15 +686,16 @@ MP_HD bool within_track(const Track& tk, double px, double py, double* dist_out,
 // are pairwise different (no tie to break by index): then the argmin is two comparisons, its ring neighbours sit at fixed offsets of the padded
 // table, and no index arithmetic, list scan or point permutation is needed.  Returns false when it does not apply (first step, NaN position,
 // far from the anchor, exact ties): the caller then runs within_track, which finds the same point by the general rules -- and both end in
-// track_project, so the result never depends on the path taken.  rel (out) = nearest point - anchor in ring steps (-1, 0, +1).
+// ring_entry_project, so the result never depends on the path taken.  rel (out) = nearest point - anchor in ring steps (-1, 0, +1).
 // (device: returns the wave mask of the lanes it applies to -- compares straight into scalar registers, ANDed there -- and the caller tests
 // "all lanes"; going through a per-lane bool and __all costs two more vector instructions per evaluation)
 MP_HD unsigned long long ring_candidates(const double* ring, const double* cert, int a0, double px, double py, double m2x, double m2y, int* rel) {
     const int a = a0 < 0 ? 0 : a0;                                             // branch-free: a missing anchor reads entry 0 and reports "not applicable"
-    const double* e0 = ring + (size_t)4 * (a + kRingPad);
+    constexpr int S = kRingStride;
+    const double* e0 = ring + (size_t)S * (a + kRingPad);
     const double d0 = fma(e0[1], m2y, fma(e0[0], m2x, e0[2]));                 // |q|^2 - 2 q.p, as in within_track
-    const double dm = fma(e0[-3], m2y, fma(e0[-4], m2x, e0[-2]));
-    const double dp = fma(e0[5], m2y, fma(e0[4], m2x, e0[6]));
+    const double dm = fma(e0[-S + 1], m2y, fma(e0[-S], m2x, e0[-S + 2]));
+    const double dp = fma(e0[S + 1], m2y, fma(e0[S], m2x, e0[S + 2]));
     const double D02 = d0 + fma(px, px, py * py);
     *rel = (dm < d0 && dm < dp) ? -1 : ((dp < d0 && dp < dm) ? 1 : 0);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -658,12 +711,13 @@ MP_HD unsigned long long ring_candidates(const double* ring, const double* cert,
 // have to be broken by track index, which the general search does).  rel (out) in -2 .. 2.
 MP_HD unsigned long long ring5_candidates(const double* ring, const double* cert5, int a0, double px, double py, double m2x, double m2y, int* rel) {   // (wave mask, like ring_candidates)
     const int a = a0 < 0 ? 0 : a0;
-    const double* e0 = ring + (size_t)4 * (a + kRingPad);
+    constexpr int S = kRingStride;
+    const double* e0 = ring + (size_t)S * (a + kRingPad);
     const double d0 = fma(e0[1], m2y, fma(e0[0], m2x, e0[2]));
-    const double dm = fma(e0[-3], m2y, fma(e0[-4], m2x, e0[-2]));
-    const double dp = fma(e0[5], m2y, fma(e0[4], m2x, e0[6]));
-    const double dmm = fma(e0[-7], m2y, fma(e0[-8], m2x, e0[-6]));
-    const double dpp = fma(e0[9], m2y, fma(e0[8], m2x, e0[10]));
+    const double dm = fma(e0[-S + 1], m2y, fma(e0[-S], m2x, e0[-S + 2]));
+    const double dp = fma(e0[S + 1], m2y, fma(e0[S], m2x, e0[S + 2]));
+    const double dmm = fma(e0[-2 * S + 1], m2y, fma(e0[-2 * S], m2x, e0[-2 * S + 2]));
+    const double dpp = fma(e0[2 * S + 1], m2y, fma(e0[2 * S], m2x, e0[2 * S + 2]));
     const double D02 = d0 + fma(px, px, py * py);
     double best = d0; int r = 0;
     if (dm < best) { best = dm; r = -1; }
@@ -679,8 +733,7 @@ MP_HD unsigned long long ring5_candidates(const double* ring, const double* cert
 #endif
 }
 MP_HD bool ring_project(const double* ring, int a0, int rel, double px, double py, double* dist_out) {
-    const double* e = ring + (size_t)4 * (a0 + rel + kRingPad);
-    return track_project(px, py, e[0], e[1], e[-4], e[-3], e[4], e[5], e[3], dist_out);
+    return ring_entry_project(ring + (size_t)kRingStride * (a0 + rel + kRingPad), px, py, dist_out);
 }
 MP_HD int ring_wrap(int mi, int P) { return (mi < 0) ? mi + P : ((mi >= P) ? mi - P : mi); }
 
@@ -707,8 +760,8 @@ MP_HD double car_reward(const CarParams& p, const Track& tk, double x, double y,
         MPOPIS_SICK(2);
         // would a 5-point ring certificate hold?  radius = half the distance from the anchor to the nearest point outside {a-2..a+2} (brute force here)
         const int a_ = *anchor; double r2_ = INFINITY;
-        for (int j_ = 0; j_ < tk.P; ++j_) { int d_ = j_ - a_; if (d_ < 0) d_ = -d_; if (d_ > tk.P - d_) d_ = tk.P - d_; if (d_ > 2) { const double ex_ = tk.ring[4 * (j_ + kRingPad)] - tk.ring[4 * (a_ + kRingPad)], ey_ = tk.ring[4 * (j_ + kRingPad) + 1] - tk.ring[4 * (a_ + kRingPad) + 1]; r2_ = fmin(r2_, ex_ * ex_ + ey_ * ey_); } }
-        const double dx_ = x - tk.ring[4 * (a_ + kRingPad)], dy_ = y - tk.ring[4 * (a_ + kRingPad) + 1];
+        for (int j_ = 0; j_ < tk.P; ++j_) { int d_ = j_ - a_; if (d_ < 0) d_ = -d_; if (d_ > tk.P - d_) d_ = tk.P - d_; if (d_ > 2) { const double ex_ = tk.ring[kRingStride * (j_ + kRingPad)] - tk.ring[kRingStride * (a_ + kRingPad)], ey_ = tk.ring[kRingStride * (j_ + kRingPad) + 1] - tk.ring[kRingStride * (a_ + kRingPad) + 1]; r2_ = fmin(r2_, ex_ * ex_ + ey_ * ey_); } }
+        const double dx_ = x - tk.ring[kRingStride * (a_ + kRingPad)], dy_ = y - tk.ring[kRingStride * (a_ + kRingPad) + 1];
         if (!(4.0 * (dx_ * dx_ + dy_ * dy_) < r2_)) MPOPIS_SICK(4);
     }
 #endif

@@ -21,14 +21,14 @@
 
 namespace mpopis {
 
-// Track tables into LDS (dynamic LDS layout: ring table [(P+6)][4] + certification radii [2][P]; with ALL: + x, y, w, |q|^2 [4][P] + neighbour
+// Track tables into LDS (dynamic LDS layout: ring table [(P+6)][6] + certification radii [2][P]; with ALL: + x, y, w, |q|^2 [4][P] + neighbour
 // distances [P][W+1] + neighbour indices [P][W+1]).  Returns the Track the rollout uses; the caller synchronises.
 template <bool ALL>
 __device__ __forceinline__ Track stage_track(const Track& g, double* sh, int tid, int nthreads) {
     const int P = g.P, W = g.nbrw, NS = P * (W + 1);
     double* sh_ring = sh;
-    double* sh_cert = sh + 4 * (P + 2 * kRingPad);
-    for (int i = tid; i < 4 * (P + 2 * kRingPad); i += nthreads) sh_ring[i] = g.ring[i];
+    double* sh_cert = sh + kRingStride * (P + 2 * kRingPad);
+    for (int i = tid; i < kRingStride * (P + 2 * kRingPad); i += nthreads) sh_ring[i] = g.ring[i];
     for (int i = tid; i < 2 * P; i += nthreads) sh_cert[i] = g.ring_cert[i];      // three-point and five-point certificates
     if (!ALL) return Track{g.x, g.y, g.w, g.n2, P, g.nbr_idx, g.nbr_dist, W, sh_ring, sh_cert};
     double* sh_trk = sh_cert + 2 * P;
@@ -39,11 +39,11 @@ __device__ __forceinline__ Track stage_track(const Track& g, double* sh, int tid
     return Track{sh_trk, sh_trk + P, sh_trk + 2 * P, sh_trk + 3 * P, P, sh_ni, sh_nd, W, sh_ring, sh_cert};
 }
 inline size_t track_lds_bytes(int P, int W, bool all) {
-    return (size_t)(4 * (P + 2 * kRingPad) + 2 * P) * sizeof(double) + (all ? (size_t)4 * P * sizeof(double) + (size_t)P * (W + 1) * (sizeof(double) + sizeof(int)) : 0);
+    return (size_t)(kRingStride * (P + 2 * kRingPad) + 2 * P) * sizeof(double) + (all ? (size_t)4 * P * sizeof(double) + (size_t)P * (W + 1) * (sizeof(double) + sizeof(int)) : 0);
 }
 
-// TLDS: every track table fits the default 64 KB of dynamic LDS (P <= ~230 points: all bundled tracks).  Otherwise only the ring table of the
-// straight-line nearest-point search is staged (40 B per point) and the general search -- first step of a rollout, lanes far off their
+// TLDS: every track table fits the default 64 KB of dynamic LDS (P <= 190 points: all bundled tracks).  Otherwise only the ring table of the
+// straight-line nearest-point search is staged (64 B per point) and the general search -- first step of a rollout, lanes far off their
 // anchor -- reads the coordinate / neighbour tables from global memory.
 #ifdef MPOPIS_ROLL_PROF
 // dev build (tools/roll_prof.sh): start / end time (s_memrealtime, 100 MHz) and hardware id of every wave of the last 1-car launch.
@@ -458,11 +458,11 @@ void launch_step_begin(int* status, int* active, const int* alive, int* iters, c
 
 // Dynamic LDS a rollout kernel may request without raising its limit: the default 64 KB minus the kernels' STATIC LDS (two-wave kernels:
 // mailbox 4 KB + control-cost column 0.5 KB + flags + per-car bounds, ~4.7 KB).  Beyond it the limit is raised before the launch, once per
-// kernel and device, to what the largest supported track needs: the ring-only layout at kMaxTrackPoints (48 P + 192 B = 98 496 B at P = 2048)
-// plus the static part, rounded up -- 112 KB of the CU's 160 KB.
+// kernel and device, to what the largest supported track needs: the ring-only layout at kMaxTrackPoints (64 P + 288 B = 131 360 B at P = 2048)
+// plus the static part, rounded up -- 144 KB of the CU's 160 KB.
 constexpr size_t kRolloutDynLdsDefault = 56 * 1024;
-constexpr int kRolloutDynLdsRaised = 112 * 1024;
-static_assert((size_t)(4 * (kMaxTrackPoints + 2 * kRingPad) + 2 * kMaxTrackPoints) * sizeof(double) + 8 * 1024 <= (size_t)kRolloutDynLdsRaised,
+constexpr int kRolloutDynLdsRaised = 144 * 1024;
+static_assert((size_t)(kRingStride * (kMaxTrackPoints + 2 * kRingPad) + 2 * kMaxTrackPoints) * sizeof(double) + 8 * 1024 <= (size_t)kRolloutDynLdsRaised,
               "ring table of the largest track + static LDS must fit the raised limit");
 // one `seen` mask per kernel (non-type template parameter): large tracks need the dynamic-LDS limit raised, per device
 template <void (*KERNEL)(RolloutArgs)>
@@ -555,8 +555,8 @@ bool launch_rollout(const RolloutArgs& a, hipStream_t st, hipError_t* custom_err
         return true;
     }
     const int P = a.env.track.P, W = a.env.track.nbrw;
-    // every table in LDS when that fits the default 64 KB (all bundled tracks: 48-60 points); larger tracks (Track(infile; sample_factor = 1):
-    // ~1000 points) stage the ring table only (48 P + 192 B: 96.2 KB at the 2048-point limit; the kernels' dynamic-LDS limit is raised to 112 KB once)
+    // every table in LDS when that fits the default 64 KB (all bundled tracks: 48-60 points); larger tracks (beyond 190 points; Track(infile; sample_factor = 1):
+    // ~1000 points) stage the ring table only (64 P + 288 B: 128.3 KB at the 2048-point limit; the kernels' dynamic-LDS limit is raised to 144 KB once)
     const bool tl = track_lds_bytes(P, W, true) <= kRolloutDynLdsDefault;      // (static LDS of the two-wave kernels counted: P = 221, 222 used to total 65.7-66 KB without the limit being raised)
     return launch_car_rollout(a, tl, track_lds_bytes(P, W, tl), st);
 }
