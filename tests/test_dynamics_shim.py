@@ -1,7 +1,8 @@
 """CPU check (no GPU) of the engine's model step -- mpopis_amd/csrc/car_dynamics.h: car_action_step = ten car_substep's with the HOT force rules (forward, front
 slip in the forward half plane) and the GENERAL rules (stopped, sliding / rolling backwards, NaN) sharing one integration tail -- against the oracle's literal
 CarRacingEnv functor + _step! (src/envs/car_racing.jl:238-250,282-344: atan2 / tan / sincos per Euler sub-step).  The header is compiled for the host
-(tests/shim/host_shim.cpp, test infrastructure only); the device build differs from it only in the rcp / rsq seeds of its divisions and square roots.
+(tests/shim/host_shim.cpp, test infrastructure only); what the device build does differently -- rcp / rsq seeds with Newton steps, inline v_min / v_max / v_fma forms,
+wave masks, the PSI = false and renorm = false forms of the rollout kernels -- is tested by tests/test_gpu_dynamics_harness.py on the same states.
 What this pins without a GPU: a regression of the general force rules (the cold lanes of a rollout that brakes to a standstill) shows up here as a state
 deviation far above rounding -- tests/test_gpu_standstill.py and the fuzz sweep only see it through costs and controls.  States: driving, crawling, exactly
 stopped, rolling backwards, spinning (|beta| large), full brake through Vx = 0, steering at the stops; actions incl. the clamp values."""
@@ -10,6 +11,7 @@ import os
 import subprocess
 import numpy as np
 import pytest
+from tests.helpers.dynamics_cases import states as _states, random_car_params as _random_car_params
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SHIM_SRC = os.path.join(HERE, "shim", "host_shim.cpp")
@@ -26,23 +28,6 @@ def shim():
     L.shim_car_action_step.argtypes = [dp, dp, C.c_double, C.c_double]
     L.shim_car_action_step.restype = None
     return L
-
-
-def _states(rng, n, regime):
-    s = np.zeros((n, 8))
-    s[:, 0] = rng.uniform(-50, 50, n); s[:, 1] = rng.uniform(-50, 50, n); s[:, 2] = rng.uniform(-np.pi, np.pi, n)
-    s[:, 6] = rng.uniform(-0.45, 0.45, n); s[:, 7] = rng.uniform(-1, 1, n)
-    if regime == "driving":
-        s[:, 3] = rng.uniform(2.0, 35.0, n); s[:, 4] = rng.uniform(-1.5, 1.5, n); s[:, 5] = rng.uniform(-0.8, 0.8, n)
-    elif regime == "crawling":
-        s[:, 3] = rng.uniform(1e-3, 1.2, n); s[:, 4] = rng.uniform(-0.3, 0.3, n); s[:, 5] = rng.uniform(-0.3, 0.3, n)
-    elif regime == "stopped":
-        s[:, 3] = 0.0; s[:, 4] = np.where(rng.random(n) < 0.5, 0.0, rng.uniform(-0.2, 0.2, n)); s[:, 5] = np.where(rng.random(n) < 0.5, 0.0, rng.uniform(-0.2, 0.2, n))
-    elif regime == "backwards":
-        s[:, 3] = -rng.uniform(1e-3, 6.0, n); s[:, 4] = rng.uniform(-1.0, 1.0, n); s[:, 5] = rng.uniform(-0.6, 0.6, n)
-    elif regime == "spinning":
-        s[:, 3] = rng.uniform(-3.0, 8.0, n); s[:, 4] = rng.uniform(-8.0, 8.0, n); s[:, 5] = rng.uniform(-3.0, 3.0, n)
-    return s
 
 
 @pytest.mark.parametrize("regime", ["driving", "crawling", "stopped", "backwards", "spinning"])
@@ -147,20 +132,7 @@ def test_model_step_with_random_car_parameters(shim, oracle):
     base = oracle.car_default_params()
     worst, n_total = 0.0, 0
     for trial in range(300):
-        p = base.copy()
-        p[0] *= rng.uniform(0.6, 1.6); p[1] *= rng.uniform(0.6, 1.6)                    # m, Izz
-        p[2] *= rng.uniform(0.5, 1.5)                                                    # h
-        p[3] *= rng.uniform(0.8, 1.25); p[4] *= rng.uniform(0.8, 1.25)                   # lf, lr
-        p[5] *= rng.uniform(0.0, 2.0); p[6] *= rng.uniform(0.0, 2.0)                     # CD0, CD1
-        p[7] *= rng.uniform(0.5, 1.8); p[8] *= rng.uniform(0.5, 1.8)                     # Caf, Car
-        p[9] = rng.uniform(0.4, 1.2); p[10] = rng.uniform(0.4, 1.2)                      # mu_f, mu_r
-        p[11] = np.deg2rad(rng.uniform(10.0, 45.0))                                      # delta_max
-        p[12] = np.deg2rad(rng.choice([30.0, 90.0, 150.0, 400.0, 900.0]))                # delta_dot_max (the last two: beyond the small-angle range per sub-step)
-        p[13] *= rng.uniform(0.5, 1.5); p[14] *= rng.uniform(0.5, 1.5)                   # Fx_max, Fx_min
-        p[15] = rng.uniform(0.3, 0.9); p[16] = rng.uniform(0.0, 1.0)                     # lambda_brake, lambda_drive
-        p[17] = np.deg2rad(rng.uniform(15.0, 80.0))                                      # beta_limit
-        nsub = int(rng.choice([1, 2, 3, 5, 7, 10, 13, 20]))
-        p[19] = float(rng.choice([0.005, 0.01, 0.02])); p[18] = nsub * p[19]             # delta_t, dt
+        p = _random_car_params(rng, base)                                                 # tests/helpers/dynamics_cases.py
         for regime in ("driving", "crawling", "stopped", "backwards", "spinning"):
             S = _states(rng, 6, regime)
             S[:, 6] = rng.uniform(-0.9, 0.9, 6) * p[11]                                  # steering angle inside its limits

@@ -15,6 +15,7 @@ import os
 import subprocess
 import numpy as np
 import pytest
+from tests.helpers.dynamics_cases import tracks as _tracks, exact as _exact, normal as _normal, positions as _positions
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SHIM_SRC = os.path.join(HERE, "shim", "host_shim.cpp")
@@ -37,72 +38,8 @@ def shim():
     return L
 
 
-def _tracks():
-    from mpopis_amd.engine import default_track, BUNDLED_TRACKS
-    out = [(n, default_track(name=n)) for n in BUNDLED_TRACKS]
-    for P in (3, 5):
-        a = np.linspace(0, 2 * np.pi, P, endpoint=False)
-        out.append(("ring%d" % P, (30 * np.cos(a), 30 * np.sin(a), np.full(P, 15.0))))
-    return [(n, tuple(np.ascontiguousarray(a, dtype=np.float64) for a in t)) for n, t in out]
-
-
 TRACKS = _tracks()                                               # kept alive: the shim caches the tables of a track by the address of its x array
 _DUMMY = tuple(np.ascontiguousarray(a) for a in (np.array([0.0, 1.0, 0.0]), np.array([0.0, 0.0, 1.0]), np.ones(3)))
-
-
-def _exact(track, p):
-    """car_racing_tracks.jl:68-92 in long double: nearest point (first minimum), the nearer ring neighbour (ties -> predecessor), distance from the line"""
-    X, Y = track[0].astype(LD), track[1].astype(LD)
-    P = len(X)
-    px, py = LD(p[0]), LD(p[1])
-    d2 = (X - px) ** 2 + (Y - py) ** 2
-    i = int(np.argmin(d2))
-    im, ip = (i - 1) % P, (i + 1) % P
-
-    def line(j):
-        vx, vy, ux, uy = X[j] - X[i], Y[j] - Y[i], px - X[i], py - Y[i]
-        return abs(ux * vy - uy * vx) / np.sqrt(vx * vx + vy * vy)
-    rest = np.delete(d2, i)
-    return dict(i=i, prev=bool(d2[im] <= d2[ip]), dm2=d2[im], dp2=d2[ip], d_prev=line(im), d_next=line(ip), u=np.sqrt(d2[i]),
-                clear=bool(rest.min() > d2[i] * (1 + LD(1e-9)) + LD(1e-9)))          # the nearest point is not in doubt
-
-
-def _normal(track, i, j):
-    vx, vy = track[0][j] - track[0][i], track[1][j] - track[1][i]
-    n = np.hypot(vx, vy)
-    return np.array([vx / n, vy / n]), np.array([-vy / n, vx / n])
-
-
-def _positions(track, rng):
-    """(kind, position) pairs for every track point"""
-    tx, ty, tw = track
-    P = len(tx)
-    out = []
-    for i in range(P):
-        q = np.array([tx[i], ty[i]])
-        im, ip = (i - 1) % P, (i + 1) % P
-        out.append(("point", q.copy()))
-        for j in (im, ip):
-            t, n = _normal(track, i, j)
-            seg = np.hypot(tx[j] - tx[i], ty[j] - ty[i])
-            out.append(("segment", q + t * seg * rng.uniform(0.02, 0.45)))
-            out.append(("near", q + t * seg * rng.uniform(0.02, 0.4) + n * rng.normal(0.0, 3.0)))
-            for side in (-1.0, 1.0):                              # the lane edge, 1e-9 m inside and outside: moved onto it along the segment's normal below
-                for eps in (-1e-9, 1e-9):
-                    out.append(("edge", q + t * seg * rng.uniform(0.02, 0.3) + n * side * (tw[i] + eps)))
-        # the switch: the point of the perpendicular bisector of (predecessor, successor) closest to q, then one ulp either way along the chord
-        a, b = np.array([tx[im], ty[im]]), np.array([tx[ip], ty[ip]])
-        mid, ch = 0.5 * (a + b), (b - a) / np.hypot(*(b - a))
-        perp = np.array([-ch[1], ch[0]])
-        for s in (np.dot(q - mid, perp), np.dot(q - mid, perp) + 2.0, np.dot(q - mid, perp) - 2.0):
-            p = mid + s * perp
-            k = int(np.argmax(np.abs(ch)))
-            for step in (0, 1, -1):
-                pp = p.copy()
-                if step:
-                    pp[k] = np.nextafter(pp[k], pp[k] + step * np.sign(ch[k]))
-                out.append(("switch", pp))
-    return out
 
 
 def _call(shim, track, p, anchor, ring):
