@@ -103,9 +103,11 @@ struct RolloutArgs {
     int* status;                // with cmin: a non-finite cost sets MPOPIS_ERR_ACTION here (what k_weights reports when it runs)
     int share = 1;              // launches of this size in flight at once (multi-stream schedule): kernel choice goes by the chip's total load
 };
-// order-preserving map double -> uint64 (unsigned comparison == numeric comparison, NaN sorts last) for atomicMin on costs
+// order-preserving map double -> uint64 (unsigned comparison == numeric comparison, NaN sorts last) for atomicMin on costs.  Every NaN maps to the key
+// of the positive quiet NaN: the rollout's cost -= reward leaves a NaN with the sign bit SET, whose raw pattern would sort before every number.
 __host__ __device__ __forceinline__ unsigned long long cost_key(double v) {
     unsigned long long u; memcpy(&u, &v, 8);
+    if (v != v) return 0xfff8000000000000ull;
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 __host__ __device__ __forceinline__ double cost_unkey(unsigned long long k) {
@@ -135,6 +137,12 @@ __device__ __forceinline__ double slot_val(double v, int) { return v; }
 __device__ __forceinline__ double slot_val(const double* v, int b) { return v[b]; }
 struct SlotVal { double v; const double* per_slot; };   // per_slot == nullptr: v in every slot; else per_slot[b] (a [B] device array that moves with the slot views)
 
+// The kernel launch_rollout picks, as a pure function of the launch's arguments (the launcher switches on it; tools/kbench_rollout.hip writes it into
+// its result so that a test written for one form fails when a threshold moves): the body, whether the trajectory logger is on, whether every track
+// table is staged in LDS (car bodies: otherwise the ring table only; custom body: the env's data table goes to the code object's LDS kernel), and the dynamic LDS of one workgroup.  MPOPIS_ROLLOUT_DUO is read once per process.
+enum RolloutBody { ROLLOUT_SIMPLE2 = 0, ROLLOUT_SIMPLE4 = 1, ROLLOUT_CUSTOM = 2, ROLLOUT_TWO_WAVE = 3, ROLLOUT_ONE_WAVE_SPB1 = 4, ROLLOUT_ONE_WAVE_SPB4 = 5 };
+struct RolloutForm { RolloutBody body = ROLLOUT_SIMPLE2; bool log = false, tlds = false; size_t lds = 0; };
+RolloutForm rollout_form(const RolloutArgs& a);
 bool launch_rollout(const RolloutArgs& a, hipStream_t s, hipError_t* custom_err = nullptr);      // false: nothing launched -- no rollout kernel for this env, or the custom env's launch failed (*custom_err says why)
 void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t s, const Track& tk);
 // (iters_acc: per-slot running sum of the iteration counts of earlier steps, folded in before iters is cleared; may be null)

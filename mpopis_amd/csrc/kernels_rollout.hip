@@ -502,19 +502,16 @@ static long long rollout_duo_max_waves(int ncars) {
     return env_duo >= 0 ? env_duo : (long long)(ncars == 1 ? kDuoCarWaves : kDuoCarsWaves) * coop_max_workgroups();
 }
 
-// NC cars (compile-time dispatch over 1..kMaxCars): the two-wave form for few rollout waves, otherwise the one-wave form with one sample-wave per
-// workgroup for small K (every wave on its own CU) or 4 sharing the LDS tables for large K.  False: no kernel for this car count.
+// NC cars (compile-time dispatch over 1..kMaxCars): the body rollout_form chose.  False: no kernel for this car count.
 template <int NC = 1>
-static bool launch_car_rollout(const RolloutArgs& a, bool tl, size_t lds, hipStream_t st) {
+static bool launch_car_rollout(const RolloutArgs& a, const RolloutForm& f, hipStream_t st) {
     if (a.env.ncars != NC) {
-        if constexpr (NC < kMaxCars) return launch_car_rollout<NC + 1>(a, tl, lds, st);
+        if constexpr (NC < kMaxCars) return launch_car_rollout<NC + 1>(a, f, st);
         else return false;
     }
-    constexpr int S = 64 / NC;
-    const long long waves = (long long)a.B * ((a.K + S - 1) / S) * std::max(1, a.share);
-    if (!a.traj && waves <= rollout_duo_max_waves(NC)) launch_two_wave<NC>(a, tl, lds, st);
-    else if (a.K >= 1024) launch_one_wave<NC, 4>(a, tl, lds, st);
-    else launch_one_wave<NC, 1>(a, tl, lds, st);
+    if (f.body == ROLLOUT_TWO_WAVE) launch_two_wave<NC>(a, f.tlds, f.lds, st);
+    else if (f.body == ROLLOUT_ONE_WAVE_SPB4) launch_one_wave<NC, 4>(a, f.tlds, f.lds, st);
+    else launch_one_wave<NC, 1>(a, f.tlds, f.lds, st);
     return true;
 }
 
@@ -522,7 +519,7 @@ static bool launch_car_rollout(const RolloutArgs& a, bool tl, size_t lds, hipStr
 // every kind that is not the car as one of the two simple envs, so a custom handle must never reach them.
 // An env with a table: four-wave workgroups; a table the code object's LDS kernel can stage goes there with ntab * 8 bytes of dynamic LDS (a small
 // table costs no occupancy), a larger one to the kernel that reads it from global memory.
-static bool launch_custom_rollout(const RolloutArgs& a, hipStream_t st, hipError_t* err) {
+static bool launch_custom_rollout(const RolloutArgs& a, const RolloutForm& f, hipStream_t st, hipError_t* err) {
     const CustomEnv* ce = a.env.custom;
     if (!ce || !ce->rollout) { if (err) *err = hipErrorInvalidHandle; return false; }
     mpopis_env_rollout_tab_args kt{};
@@ -535,10 +532,10 @@ static bool launch_custom_rollout(const RolloutArgs& a, hipStream_t st, hipError
     hipError_t e;
     if (ce->has_table) {
         kt.table = (uint64_t)ce->table_view; kt.table_stride = ce->table_stride; kt.ntab = ce->ntab;
-        const bool lds = ce->ntab <= ce->table_lds_doubles;
+        const bool lds = f.tlds;                                             // rollout_form: the table fits what the code object's LDS kernel stages
         constexpr int WG = MPOPIS_ENV_TABLE_THREADS;
         void* params[] = {&kt};
-        e = hipModuleLaunchKernel(lds ? ce->rollout : ce->rollout_gtab, (a.K + WG - 1) / WG, a.B, 1, WG, 1, 1, lds ? (unsigned)ce->ntab * 8u : 0u, st, params, nullptr);
+        e = hipModuleLaunchKernel(lds ? ce->rollout : ce->rollout_gtab, (a.K + WG - 1) / WG, a.B, 1, WG, 1, 1, (unsigned)f.lds, st, params, nullptr);
     } else {
         void* params[] = {&k};
         e = hipModuleLaunchKernel(ce->rollout, (a.K + 63) / 64, a.B, 1, 64, 1, 1, 0, st, params, nullptr);
@@ -547,18 +544,43 @@ static bool launch_custom_rollout(const RolloutArgs& a, hipStream_t st, hipError
     return e == hipSuccess;
 }
 
-bool launch_rollout(const RolloutArgs& a, hipStream_t st, hipError_t* custom_err) {
-    if (a.env.kind == MPOPIS_ENV_CUSTOM) return launch_custom_rollout(a, st, custom_err);
+// The kernel launch_rollout picks (engine.h).  The car env: the two-wave form for few rollout waves (never with the logger), otherwise the one-wave
+// form with one sample-wave per workgroup for small K (every wave on its own CU) or 4 sharing the LDS tables for large K.
+RolloutForm rollout_form(const RolloutArgs& a) {
+    RolloutForm f;
+    f.log = a.traj != nullptr;
+    if (a.env.kind == MPOPIS_ENV_CUSTOM) {
+        const CustomEnv* ce = a.env.custom;
+        f.body = ROLLOUT_CUSTOM;
+        if (ce && ce->has_table && ce->ntab <= ce->table_lds_doubles) { f.tlds = true; f.lds = (size_t)ce->ntab * 8u; }
+        return f;
+    }
     if (a.env.kind == MPOPIS_ENV_MOUNTAINCAR || a.env.kind == MPOPIS_ENV_CARTPOLE) {
-        const auto kernel = a.env.kind == MPOPIS_ENV_CARTPOLE ? k_rollout_simple<4> : k_rollout_simple<2>;     // state size 4 / 2
+        f.body = a.env.kind == MPOPIS_ENV_CARTPOLE ? ROLLOUT_SIMPLE4 : ROLLOUT_SIMPLE2;     // state size 4 / 2
+        return f;
+    }
+    const int P = a.env.track.P, W = a.env.track.nbrw, NC = a.env.ncars;
+    // every table in LDS when that fits the default 64 KB (all bundled tracks: 48-60 points); larger tracks (beyond 190 points; Track(infile; sample_factor = 1):
+    // ~1000 points) stage the ring table only (64 P + 288 B: 128.3 KB at the 2048-point limit; the kernels' dynamic-LDS limit is raised to 144 KB once)
+    f.tlds = track_lds_bytes(P, W, true) <= kRolloutDynLdsDefault;      // (static LDS of the two-wave kernels counted: P = 221, 222 used to total 65.7-66 KB without the limit being raised)
+    f.lds = track_lds_bytes(P, W, f.tlds);
+    if (NC < 1 || NC > kMaxCars) { f.body = ROLLOUT_ONE_WAVE_SPB1; return f; }           // (no kernel: launch_rollout returns false)
+    const int S = 64 / NC;
+    const long long waves = (long long)a.B * ((a.K + S - 1) / S) * std::max(1, a.share);
+    if (!a.traj && waves <= rollout_duo_max_waves(NC)) f.body = ROLLOUT_TWO_WAVE;
+    else f.body = a.K >= 1024 ? ROLLOUT_ONE_WAVE_SPB4 : ROLLOUT_ONE_WAVE_SPB1;
+    return f;
+}
+
+bool launch_rollout(const RolloutArgs& a, hipStream_t st, hipError_t* custom_err) {
+    const RolloutForm f = rollout_form(a);
+    if (f.body == ROLLOUT_CUSTOM) return launch_custom_rollout(a, f, st, custom_err);
+    if (f.body == ROLLOUT_SIMPLE2 || f.body == ROLLOUT_SIMPLE4) {
+        const auto kernel = f.body == ROLLOUT_SIMPLE4 ? k_rollout_simple<4> : k_rollout_simple<2>;
         hipLaunchKernelGGL(kernel, dim3((a.K + 63) / 64, a.B), dim3(64), 0, st, a);
         return true;
     }
-    const int P = a.env.track.P, W = a.env.track.nbrw;
-    // every table in LDS when that fits the default 64 KB (all bundled tracks: 48-60 points); larger tracks (beyond 190 points; Track(infile; sample_factor = 1):
-    // ~1000 points) stage the ring table only (64 P + 288 B: 128.3 KB at the 2048-point limit; the kernels' dynamic-LDS limit is raised to 144 KB once)
-    const bool tl = track_lds_bytes(P, W, true) <= kRolloutDynLdsDefault;      // (static LDS of the two-wave kernels counted: P = 221, 222 used to total 65.7-66 KB without the limit being raised)
-    return launch_car_rollout(a, tl, track_lds_bytes(P, W, tl), st);
+    return launch_car_rollout(a, f, st);
 }
 
 }  // namespace mpopis

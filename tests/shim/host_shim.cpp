@@ -108,3 +108,27 @@ extern "C" void shim_dyn_reward(const double* p20, int P, const double* tx, cons
         memcpy(&o[9], &m3, 8); memcpy(&o[10], &m5, 8); memcpy(&o[11], &ex, 8);
     }
 }
+// ---- one car of a rollout as kernels_rollout.hip carries it (tests/test_rollout_cases_cpu.py): the start state extended once (sin / cos; the anchor of the
+// first search by the full scan, as write_xext), the actions as given (already clamped), the unit-circle renormalisation every 4th step.  n cars at once on
+// one track: states[n][T][8] after every step, rew[n][T] the car's own reward of the step (no pair terms: the caller adds them), near[n] the start anchor
+extern "C" void shim_car_rollout_log(const double* p20, int P, const double* tx, const double* ty, const double* tw, int n, const double* s8, const double* ctrl, int T,
+                                     double* states, double* rew, int* near) {
+    const CarParams p = make_car_params(p20);
+    std::vector<double> n2; Track tk = mk(P, tx, ty, tw, n2);
+    for (int i = 0; i < n; ++i) {
+        CarState st; car_state_from8(st, s8 + (size_t)i * 8);
+        double dist; int a = -1;
+        (void)within_track(tk, st.x, st.y, &dist, &a);
+        st.near = a; near[i] = a;
+        for (int t = 0; t < T; ++t) {
+            car_action_step<true>(p, st, ctrl[((size_t)i * T + t) * 2], ctrl[((size_t)i * T + t) * 2 + 1], (t & 3) == 0);
+            rew[(size_t)i * T + t] = car_reward(p, tk, st.x, st.y, st.Vx, st.Vy, &st.near);
+            car_state_to8(st, states + ((size_t)i * T + t) * 8);
+        }
+    }
+}
+// the two simple envs' step and reward (engine.h's simple_env_step / simple_env_reward restated on the header's functions): kind 0 mountaincar (p8), 2 cartpole (p11)
+extern "C" double shim_simple_step(int kind, const double* prm, double* s, int* t, int* done, double a) {
+    if (kind == 2) { const CpParams p = make_cp_params(prm); cp_step(p, s, t, done, a); return cp_reward(*done); }
+    const McParams p = make_mc_params(prm); mc_step(p, s, t, done, a); return mc_reward(p, s, *done);
+}

@@ -1,0 +1,177 @@
+"""The rollout launcher -- every body of mpopis_amd/csrc/kernels_rollout.hip: k_rollout_simple<2 | 4>, the two-wave body, the one-wave body with one and
+with four sample-waves per workgroup, with and without the trajectory logger, with every track table in LDS and with the ring table only, for 1..8 cars
+-- and the step-begin launcher, exercised directly, below the policy level, through the C++ harness tools/kbench_rollout.hip: one process per case
+file (the launches of a file share the settings read once per process), inputs written by the test, raw device outputs read back.  The harness holds
+no reference arithmetic, fills every output with 0xA5 and gives it 64 guard entries (checked on every read).  Cases, references and checks are those
+of tests/helpers/rollout_cases.py; tests/test_rollout_cases_cpu.py shows on the CPU that the cases are what they claim and that each checker refuses
+the corruption it is meant for.  Every launch asserts the form rollout_form reported against the form restated from the constants in the sources.
+
+(a) form: the two-wave limit at waves == limit and limit + 1 (pinned by MPOPIS_ROLLOUT_DUO, once with share = 2, once by the default limit of a two-CU
+    device), K = 1023 / 1024, traj never two-wave, P on both sides of the LDS limit.
+(b) parity with OraclePolicy.simulate_model at RTOL = 1e-8 (floor 1e-9, tests/test_gpu_parity.py): 1..8 cars x three bodies, K in {1, S - 1, S, S + 1,
+    2 S + 3} (SPB 4: 1024 + S + 1), T in {1, 2, 3, 4, 5, 8, 9} for 1 and 3 cars and {1, 5} otherwise, two slots (reset grid; coincident cars and the
+    -11000 contact term), per-car asymmetric bounds, far-out samples, start states by launch_extend_state and by launch_step_begin, both table placements.
+(c) the logger form step by step for 1, 3, 6 cars x SPB 1 / SPB 4 x both table placements at T = 9: every logged state against oracle.car_step from the
+    state logged before it at 1e-11 with none set aside, the cost against the long-double sum of the oracle's rewards at the logged states (RATIO).
+(d) exact invariants, bit for bit, at every car count: column permutation, column-only dependence (SPB 4 against SPB 1), two-wave against one-wave, slot
+    alone, inactive slot untouched, iters, (U + d, E - d), zero gvec, NaN containment and status, +-inf clamped, cmin against its definition.
+(e) gamma != 0 for one and four cars against the long-double control cost (RATIO).
+(f) k_rollout_simple for MountainCar and CartPole against the oracle at 1e-12: K in {1, 63, 64, 65, 130} x T in {1, 15}, t0 / done0 given and null, a
+    start that is done, termination inside the rollout, the traj layout, a NaN action.
+(g) launch_step_begin: the first-minimum anchor under exact ties in one thread, across waves, in neighbouring lanes and across the wrap for P in {1, 2,
+    5, 63, 64, 65, 255, 256, 257, 300, 2048} and 1, 3, 8 cars against NumPy's exact argmin and launch_extend_state, and the flags and copies.
+
+The simple envs' costs are held to 1e-12 by the relative error of tests/test_gpu_parity.py (floor 1e-9), as test_level1_mountaincar holds them; their logged
+trajectories are held to 1e-12 relative to max(1, |ref|) instead -- an absolute 1e-12 for states below 1, which pass through zero -- a different metric.
+
+Found by (d): cost_key gave a NaN with its sign bit set, which is what cost -= reward leaves, the SMALLEST key; fixed in engine.h (every NaN sorts last).
+
+Measured on the MI355X (every run prints its own; DESIGN.md, "Launch-level tests of the rollout and step-begin kernels", has the same): (b) worst deviation
+from the oracle, two-wave = SPB 1 / SPB 4: 1 car 1.9e-15 / 2.4e-15, 2 cars 1.1e-15 / 1.4e-15, 3 cars 3.0e-15 / 2.6e-15, 4 cars 5.5e-14 / 7.8e-15, 5 cars 2.4e-15 /
+3.6e-15, 6 cars 8.9e-16 / 1.3e-15, 7 cars 1.9e-16 / 3.7e-16, 8 cars 3.7e-16 / 3.7e-16; (c) RATIO LOGGER <= 0.0005, states <= 3.2e-15 per step, none set aside;
+(e) RATIO GAMMA 0.074 (1 car), 0.014 (4 cars); (f) MountainCar 5.5e-16, CartPole 6.8e-16."""
+import os, shutil, subprocess
+import numpy as np
+import pytest
+from tests.helpers import rollout_cases as RC
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
+BODIES = (RC.TWO_WAVE, RC.SPB1, RC.SPB4)
+
+
+@pytest.fixture(scope="module")
+def harness():
+    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("hipcc not available to build the harness")
+    from mpopis_amd import build
+    build.build()                                                     # the harness links the library's object files
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_rollout.sh")], capture_output=True, text=True, timeout=600)
+    exe = os.path.join(ROOT, "tools", "kbench_rollout_bin")
+    assert out.returncode == 0 and os.path.exists(exe), out.stdout + out.stderr
+    return exe
+
+
+def _run(exe, tmp_path, launches, env):
+    fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "result.bin")
+    with open(fin, "wb") as f:
+        f.write(RC.pack(launches))
+    if os.path.exists(fout):
+        os.remove(fout)
+    e = dict(os.environ)
+    for k in ("MPOPIS_ROLLOUT_DUO", "MPOPIS_COOP_MAX_WG"):
+        e.pop(k, None)
+    e.update(env)
+    try:
+        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120, env=e)
+    except subprocess.TimeoutExpired as t:
+        pytest.exit("tools/kbench_rollout_bin hung: %s" % str(t.stdout)[-2000:], returncode=3)      # a hang: nothing more is started on this GPU either
+    if r.returncode < 0 or r.returncode in (134, 139) or "HIP error" in r.stdout:
+        # a fault, an abort or a crash of the harness: nothing more is started on this GPU -- the session ends here with what the process left
+        pytest.exit("tools/kbench_rollout_bin died (%s): %s" % (r.returncode, (r.stdout + r.stderr)[-2000:]), returncode=3)
+    assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
+    with open(fout, "rb") as f:
+        res = RC.unpack_result(f.read(), launches)                       # checks every guard
+    for L, R in zip(launches, res):
+        if L["op"] == RC.OP_ROLLOUT:
+            RC.check_form(L, R, *RC.env_form_args(env))
+    return res
+
+
+def _duo(body):
+    return {"MPOPIS_ROLLOUT_DUO": str(RC.duo_of(body))}
+
+
+# ================================================================ (a) form ====================================================================
+def test_form_thresholds(harness, tmp_path, oracle):
+    cases = RC.form_cases()
+    seen = set()
+    for env in sorted({tuple(sorted(c[2].items())) for c in cases}):
+        group = [c for c in cases if tuple(sorted(c[2].items())) == env]
+        res = _run(harness, tmp_path, [c[1] for c in group], dict(env))
+        for (name, L, _, body), R in zip(group, res):
+            RC.check_form(L, R, *RC.env_form_args(dict(env)), want_body=body)
+            RC.check_slots(L, R)
+            RC.check_parity(oracle, L, R, what=name)
+            seen.add(R["form"][:3])
+    want = {(b, False, t) for b in (RC.TWO_WAVE, RC.SPB1) for t in (True, False)} | {(RC.SPB4, False, True), (RC.SPB1, True, True), (RC.SPB4, True, True)}
+    assert want <= seen, want - seen
+
+
+# ================================================================ (b) parity ==================================================================
+@pytest.mark.parametrize("body", BODIES, ids=["two_wave", "spb1", "spb4"])
+@pytest.mark.parametrize("nc", range(1, 9))
+def test_parity_with_the_oracle_at_short_horizons(harness, tmp_path, oracle, nc, body):
+    Ls = RC.parity_launches(nc, body)
+    res = _run(harness, tmp_path, Ls, _duo(body))
+    worst = 0.0
+    for L, R in zip(Ls, res):
+        assert R["form"][0] == body, (RC.BODY_NAME[R["form"][0]], RC.BODY_NAME[body])
+        RC.check_slots(L, R)
+        worst = max(worst, RC.check_parity(oracle, L, R, what="K %d T %d P %d" % (L["K"], L["T"], L["P"])))
+    assert {R["form"][2] for R in res} == {True, False}                  # both table placements
+    print("\n[rollout parity] %d cars, %s: worst deviation from the oracle %.2e over %d launches (bound %.0e)" % (nc, RC.BODY_NAME[body], worst, len(Ls), RC.RTOL))
+
+
+# ================================================================ (c) the logger, step by step ================================================
+@pytest.mark.parametrize("nc", [1, 3, 6])
+def test_logger_form_step_by_step(harness, tmp_path, oracle, nc):
+    Ls = RC.logger_launches(nc)
+    res = _run(harness, tmp_path, Ls, _duo(RC.SPB1))
+    assert [R["form"][:3] for R in res] == [(RC.SPB1, True, True), (RC.SPB1, True, False), (RC.SPB4, True, True), (RC.SPB4, True, False)]
+    print()
+    for L, R in zip(Ls, res):
+        RC.check_slots(L, R)
+        dev, ratio = RC.check_logger(oracle, L, R, what="K %d P %d" % (L["K"], L["P"]))
+        print("RATIO LOGGER %.4f  (%d cars, %s, tables %s: worst state deviation per step %.2e, bound 1e-11)" %
+              (ratio, nc, RC.BODY_NAME[R["form"][0]], "in LDS" if R["form"][2] else "in global memory", dev))
+
+
+# ================================================================ (d) exact invariants ========================================================
+@pytest.mark.parametrize("nc", range(1, 9))
+def test_exact_invariants_bit_for_bit(harness, tmp_path, nc):
+    A, two, notes = RC.invariant_launches(nc)
+    RA = dict(zip(A, _run(harness, tmp_path, list(A.values()), _duo(RC.SPB1))))
+    RB = dict(zip(two, _run(harness, tmp_path, [A[n] for n in two], _duo(RC.TWO_WAVE))))
+    assert RA["base"]["form"][0] == RC.SPB1 and RA["big"]["form"][0] == RC.SPB4 and RA["logged"]["form"][:2] == (RC.SPB1, True)
+    assert all(R["form"][0] == RC.TWO_WAVE for R in RB.values())
+    RC.check_invariants(nc, A, RA, RB, two, notes)
+
+
+# ================================================================ (e) gamma != 0 ==============================================================
+@pytest.mark.parametrize("body", [RC.TWO_WAVE, RC.SPB1], ids=["two_wave", "spb1"])
+@pytest.mark.parametrize("nc", [1, 4])
+def test_control_cost_against_long_double(harness, tmp_path, oracle, nc, body):
+    L1, L0 = RC.gamma_launches(nc)
+    R1, R0 = _run(harness, tmp_path, [L1, L0], _duo(body))
+    assert R1["form"][0] == body
+    assert RC.check_parity(oracle, L0, R0) < RC.RTOL
+    q = RC.check_gamma(oracle, L1, R1, R0)
+    print("\nRATIO GAMMA %.4f  (%d cars, %s)" % (q, nc, RC.BODY_NAME[body]))
+    assert q <= 1.0, q
+
+
+# ================================================================ (f) the simple envs =========================================================
+@pytest.mark.parametrize("kind", [RC.ENV_MC, RC.ENV_CP], ids=["mountaincar", "cartpole"])
+def test_simple_envs_against_the_oracle(harness, tmp_path, oracle, kind):
+    Ls = RC.simple_launches(kind)
+    res = _run(harness, tmp_path, Ls, {})
+    worst = 0.0
+    for L, R in zip(Ls[:-1], res[:-1]):
+        assert R["form"][0] == (RC.SIMPLE4 if kind == RC.ENV_CP else RC.SIMPLE2)
+        RC.check_slots(L, R)
+        e = RC.check_parity(oracle, L, R, what="K %d T %d" % (L["K"], L["T"]))         # cost and, where logged, the [B][K][ss][T] trajectory
+        assert e < 1e-12, (L["K"], L["T"], e)
+        worst = max(worst, e)
+    nan = np.isnan(Ls[-1]["E"]).any(axis=1)
+    assert np.array_equal(np.isnan(res[-1]["cost"]), nan), "a NaN action must poison its sample's cost and no other"
+    assert np.array_equal(RC.bits(res[-1]["cost"][~nan]), RC.bits(res[-2]["cost"][~nan]))
+    print("\n[rollout simple] %s: worst deviation from the oracle %.2e over %d launches (bound 1e-12)" % ("cartpole" if kind == RC.ENV_CP else "mountaincar", worst, len(Ls) - 1))
+
+
+# ================================================================ (g) step begin ==============================================================
+def test_step_begin_anchor_ties_flags_and_copies(harness, tmp_path):
+    Ls = RC.begin_launches()
+    res = _run(harness, tmp_path, Ls, {})
+    for L, R in zip(Ls, res):
+        RC.check_begin(L, R)
