@@ -63,7 +63,11 @@ extern "C" {
  *    Later gained THREE more entry points, mpopis_set_slot_hyper, mpopis_get_slot_hyper and mpopis_set_Sigma_slots: λ, α, λ_ais, σ (step_factor
  *    under :nesmppi) and pol.Σ per trial slot, so that one resident batch can sweep them.  mpopis_config and every other entry point are unchanged,
  *    and a handle that never calls them runs what it ran before; a library that predates them does not export the symbols, which is how a caller
- *    detects support. */
+ *    detects support.
+ *    Later gained TWO more entry points, mpopis_set_env_params_slots and mpopis_set_tracks: the parameter vector of the built-in envs and the
+ *    track of the car env per trial slot, so that one resident batch can hold a policy's trials on several tracks or a robustness study over
+ *    car parameters.  mpopis_config and every other entry point are unchanged, and a handle that never calls them runs what it ran before; a
+ *    library that predates them does not export the symbols, which is how a caller detects support. */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -177,6 +181,29 @@ int  mpopis_set_env_params(mpopis_handle *h, const double *p, int32_t n);   /* e
 int  mpopis_set_env_table(mpopis_handle *h, const double *data, int64_t n, int32_t per_slot);
 int  mpopis_set_track(mpopis_handle *h, const double *x, const double *y, const double *w, int32_t P);
                                                                   /* env.track.{x′,y′,lane_width′} car_racing_tracks.jl:21-23 */
+/* Per-slot env parameters and tracks: slot b behaves like a handle given p[b*n .. b*n+n) through mpopis_set_env_params and track
+ * track_of_slot[b] through mpopis_set_track.  They hold for mpopis_rollout_costs, mpopis_policy_step, mpopis_policy_call, mpopis_env_step,
+ * mpopis_env_query, mpopis_run_trials and mpopis_bench_policy_steps.  Action bounds, K, H and N stay shared.
+ *   mpopis_set_env_params_slots  B vectors of n doubles: n = 20 on a car handle (all cars of a multi-car slot share the slot's vector), 8 on
+ *                                MountainCar, 11 on CartPole.  MPOPIS_ERR_ARG: another n, NULL p, a custom handle (per-slot data of a custom
+ *                                env goes through mpopis_set_env_table(..., per_slot)).  mpopis_set_env_params afterwards returns the handle
+ *                                to one shared vector.
+ *   mpopis_set_tracks            car handles only.  ntracks tracks, track i with P[i] points (2..2048 each); x, y, w hold them one after the
+ *                                other (sum of P doubles each).  Slot b drives on track track_of_slot[b] (0-based); NULL: ntracks must equal
+ *                                B and slot b gets track b.  Every track is uploaded once, however many slots refer to it.  MPOPIS_ERR_ARG
+ *                                with the offending track or slot in mpopis_last_error: a P[i] or a track_of_slot[b] out of range, a NULL
+ *                                array, a handle of another env kind.  Either this call or mpopis_set_track satisfies the calls that need a
+ *                                track; mpopis_set_track afterwards returns the handle to one shared track.
+ * Every slot of a launch runs one rollout kernel, chosen by the handle's LARGEST track (every table in LDS up to 190 points, beyond that the
+ * ring table only); a slot's costs can therefore differ in the last bits from those of a one-slot handle on the same track when the two fall on
+ * different sides of that limit.
+ * The tracks of every mpopis_set_track / mpopis_set_tracks call stay allocated until mpopis_destroy (about 170 bytes per track point): a
+ * study that swaps track sets very many times should do so on fresh handles.
+ * Setup calls like mpopis_set_slot_hyper below: they wait for everything the handle has queued before they write; a refused call leaves the
+ * handle as it was; the per-slot arrays are allocated at the first call (MPOPIS_ERR_HIP when that fails, the handle then stays shared). */
+int  mpopis_set_env_params_slots(mpopis_handle *h, const double *p /* B*n */, int32_t n);
+int  mpopis_set_tracks(mpopis_handle *h, int32_t ntracks, const int32_t *P, const double *x, const double *y, const double *w,
+                       const int32_t *track_of_slot /* B or NULL */);
 int  mpopis_set_action_bounds(mpopis_handle *h, const double *lo, const double *hi); /* action_space(env) */
 int  mpopis_reset(mpopis_handle *h);                       /* reset!(env) per slot: car_racing.jl:215-223, multi :160-180 */
 int  mpopis_set_state(mpopis_handle *h, const double *x /* B*ss */, const int32_t *t, const int32_t *done);
@@ -193,7 +220,7 @@ int  mpopis_set_Sigma(mpopis_handle *h, const double *Sigma, int32_t n);    /* p
 /* Per-slot policy hyper-parameters and pol.Σ: slot b behaves like a handle created with lambda[b], alpha[b], lambda_ais[b], cma_sigma[b]
  * and given Sigma[b] through mpopis_set_Sigma (γ_b = λ_b (1 - α_b); :imppi weighs its AIS iterations with λ_b).  They hold for
  * mpopis_policy_step, mpopis_policy_call, mpopis_run_trials, mpopis_bench_policy_steps and mpopis_rollout_costs (γ_b scales the one
- * Sigma_inv that call is given).  K, H, N, elite_threshold, the estimator, action bounds and env parameters stay shared.
+ * Sigma_inv that call is given).  K, H, N, elite_threshold, the estimator and action bounds stay shared (env parameters and tracks: mpopis_set_env_params_slots / mpopis_set_tracks above).
  *   mpopis_set_slot_hyper   each pointer is B doubles, or NULL = "the config's value in every slot"; four NULLs return the handle to the
  *                           shared scalars.  Accepts what mpopis_create accepts for the same fields (MPOPIS_ERR_ARG only for a non-finite
  *                           step_factor under :nesmppi).  With per-slot lambda_ais, :μΣaismppi on a car env computes the AIS weights in a launch

@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "mpopis_env_query", "mpopis_get_trajectories", "mpopis_set_state_noise", "mpopis_run_trials", "mpopis_timing_enable", "mpopis_timing_read",
     "mpopis_timing_reset", "mpopis_bench_policy_steps",
     "mpopis_create_custom", "mpopis_set_env_table", "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
-    "mpopis_set_slot_hyper", "mpopis_get_slot_hyper", "mpopis_set_Sigma_slots",
+    "mpopis_set_slot_hyper", "mpopis_get_slot_hyper", "mpopis_set_Sigma_slots", "mpopis_set_env_params_slots", "mpopis_set_tracks",
 ]
 
 
@@ -78,6 +78,9 @@ def lib():
             L.mpopis_set_slot_hyper.argtypes = [H, _dp, _dp, _dp, _dp]
             L.mpopis_get_slot_hyper.argtypes = [H, _dp, _dp, _dp, _dp]
             L.mpopis_set_Sigma_slots.argtypes = [H, _dp, C.c_int32]
+        if hasattr(L, "mpopis_set_env_params_slots"):           # (per-slot env parameters and tracks: newer still)
+            L.mpopis_set_env_params_slots.argtypes = [H, _dp, C.c_int32]
+            L.mpopis_set_tracks.argtypes = [H, C.c_int32, _ip, _dp, _dp, _dp, _ip]
         L.mpopis_destroy.argtypes = [H]
         L.mpopis_destroy.restype = None
         L.mpopis_set_env_params.argtypes = [H, _dp, C.c_int32]

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmpopis_hip.so")
-SOURCES = ["engine_api.hip", "engine_ais.hip", "engine_harness.hip", "engine_comm.hip", "kernels_rollout.hip", "kernels_reweight.hip",
+SOURCES = ["engine_api.hip", "engine_ais.hip", "engine_harness.hip", "engine_comm.hip", "kernels_rollout.hip", "kernels_rollout_slots.hip", "kernels_reweight.hip",
            "kernels_sample.hip", "kernels_linalg.hip", "kernels_select.hip", "kernels_ce.hip", "kernels_cma.hip", "kernels_invsqrt.hip", "kernels_mfma.hip",
            "kernels_nes.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
@@ -33,7 +33,9 @@ def build(force=False, verbose=False):
         sp = os.path.join(CSRC, src)
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(obj)
-        if not force and _newer(obj, [sp] + headers):
+        deps = []
+        _quoted_includes(sp, deps)                      # (kernels_rollout_slots.hip includes kernels_rollout.hip)
+        if not force and _newer(obj, deps + headers):
             continue
         cmd = [hipcc] + FLAGS + ["-c", sp, "-o", obj]
         if verbose:

@@ -73,6 +73,31 @@ struct EnvDesc {
     const CustomEnv* custom;   // MPOPIS_ENV_CUSTOM only
 };
 
+// dynamic LDS the rollout kernels' stage_track fills for a track of P points with W-wide neighbour tables (kernels_rollout.hip): the ring table and its
+// certificates, with `all` also x, y, w, |q|^2 and the neighbour tables
+inline size_t track_lds_bytes(int P, int W, bool all) {
+    return (size_t)(kRingStride * (P + 2 * kRingPad) + 2 * P) * sizeof(double) + (all ? (size_t)4 * P * sizeof(double) + (size_t)P * (W + 1) * (sizeof(double) + sizeof(int)) : 0);
+}
+
+// The env of a handle whose trial slots differ (mpopis_set_env_params_slots / mpopis_set_tracks): [B] arrays of ready-made
+// parameter structs and track descriptors that move with the slot views.  A null pointer: that part of the shared EnvDesc holds in every slot.
+// lds_all / lds_ring: track_lds_bytes of the handle's LARGEST track with every table / the ring table only -- every slot of a launch runs one kernel.
+struct SlotEnv {
+    const CarParams* car = nullptr;
+    const McParams* mc = nullptr;
+    const CpParams* cp = nullptr;
+    const Track* track = nullptr;
+    size_t lds_all = 0, lds_ring = 0;
+    bool any() const { return car || mc || cp || track; }
+};
+// the small kernels (env step / query, harness bookkeeping, the simple envs' rollout) overwrite their by-value EnvDesc with slot b's parts
+__device__ __forceinline__ void slot_env_into(EnvDesc& env, const SlotEnv& se, int b) {
+    if (se.car) env.car = se.car[b];
+    if (se.mc) env.mc = se.mc[b];
+    if (se.cp) env.cp = se.cp[b];
+    if (se.track) env.track = se.track[b];
+}
+
 // the two scalar-action classic-control envs share one code path ("simple" envs): ss = 2 or 4, as = 1
 MP_HD void simple_env_step(const EnvDesc& env, double* s, int* t, int* done, double a) {
     if (env.kind == MPOPIS_ENV_CARTPOLE) cp_step(env.cp, s, t, done, a);
@@ -102,6 +127,7 @@ struct RolloutArgs {
     unsigned long long* cmin;   // nullptr or [B]: running minimum of the slot's costs as an order-preserving key (cost_key), car kernels only
     int* status;                // with cmin: a non-finite cost sets MPOPIS_ERR_ACTION here (what k_weights reports when it runs)
     int share = 1;              // launches of this size in flight at once (multi-stream schedule): kernel choice goes by the chip's total load
+    SlotEnv senv;               // per-slot env (last: the kernel-argument offsets of everything above are those of a handle without one)
 };
 // order-preserving map double -> uint64 (unsigned comparison == numeric comparison, NaN sorts last) for atomicMin on costs.  Every NaN maps to the key
 // of the positive quiet NaN: the rollout's cost -= reward leaves a NaN with the sign bit SET, whose raw pattern would sort before every number.
@@ -144,10 +170,10 @@ enum RolloutBody { ROLLOUT_SIMPLE2 = 0, ROLLOUT_SIMPLE4 = 1, ROLLOUT_CUSTOM = 2,
 struct RolloutForm { RolloutBody body = ROLLOUT_SIMPLE2; bool log = false, tlds = false; size_t lds = 0; };
 RolloutForm rollout_form(const RolloutArgs& a);
 bool launch_rollout(const RolloutArgs& a, hipStream_t s, hipError_t* custom_err = nullptr);      // false: nothing launched -- no rollout kernel for this env, or the custom env's launch failed (*custom_err says why)
-void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t s, const Track& tk);
+void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t s, const Track& tk, const Track* slot_tk = nullptr /* [B], or null: tk in every slot */);
 // (iters_acc: per-slot running sum of the iteration counts of earlier steps, folded in before iters is cleared; may be null)
 void launch_step_begin(int* status, int* active, const int* alive, int* iters, const double* U, double* Uin, double* Ucur, int B, int cs,
-                       const double* x, double* xext, int ncars, hipStream_t st, unsigned long long* cmin, const Track& tk, unsigned long long* iters_acc = nullptr);
+                       const double* x, double* xext, int ncars, hipStream_t st, unsigned long long* cmin, const Track& tk, unsigned long long* iters_acc = nullptr, const Track* slot_tk = nullptr);
 
 // compute_weights (utils.jl:79-86) per slot: w = exp(-(1/λ)(c-min c)) / Σ, given -1/λ
 void launch_weights(const double* cost, double* w, int B, int K, SlotVal neg_inv_lambda, const int* active,
@@ -173,9 +199,9 @@ void launch_transpose_out(const double* src_rows, const double* shiftA, const do
 // real env step + reward for the resident envs
 // (both return the launch status of a custom env's kernel; hipSuccess for the built-in envs, whose launches show in hipGetLastError)
 hipError_t launch_env_step(const EnvDesc& env, double* x, int* t, int* done, const double* action,
-                           double* reward, int* status, const int* alive, int B, hipStream_t s);
+                           double* reward, int* status, const int* alive, int B, hipStream_t s, const SlotEnv& senv = SlotEnv());
 
-hipError_t launch_env_query(const EnvDesc& env, const double* x, const int* t, const int* done, double* reward, int* within, double* dist, double* beta, int B, hipStream_t s);
+hipError_t launch_env_query(const EnvDesc& env, const double* x, const int* t, const int* done, double* reward, int* within, double* dist, double* beta, int B, hipStream_t s, const SlotEnv& senv = SlotEnv());
 
 // kernels_sample.hip
 void launch_sample_normal(double* Z, int B, int cs, int K, int as, int mppi_order, const uint64_t* seeds,

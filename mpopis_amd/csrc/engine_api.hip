@@ -10,6 +10,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 using namespace mpopis;
@@ -468,7 +469,66 @@ int mpopis_set_env_params(mpopis_handle* h, const double* p, int32_t n) {
         if (n != MPOPIS_MOUNTAINCAR_NPARAMS) { h->err = "MountainCar expects 8 parameters"; return MPOPIS_ERR_ARG; }
         h->env.mc = make_mc_params(p);
     }
+    if (h->env_params_slots_on || h->track_slots_on) {         // (after mpopis_set_env_params_slots: back to one shared vector)
+        if (const int rc = quiesce(h)) return rc;
+        h->env_params_slots_on = false;
+        return h->sync_slot_env();
+    }
     return MPOPIS_OK;
+}
+
+// Car handles: while exactly one of the per-slot arrays is in force, fill the other with B copies of the shared value (engine_handle.h).  The caller
+// has quiesced the handle.  (A shared track that is not set yet gives descriptors with P = 0: track_missing() then refuses the calls that need one.)
+int mpopis_handle::sync_slot_env() {
+    if (env.kind != MPOPIS_ENV_CAR || env_params_slots_on == track_slots_on) return MPOPIS_OK;
+    const char* msg = "hipMalloc of the per-slot env arrays failed";
+    if (track_slots_on) {
+        if (slot_alloc(d_car_sl, 1)) { (void)hipGetLastError(); err = msg; return MPOPIS_ERR_HIP; }
+        const std::vector<CarParams> host((size_t)B_full, env.car);
+        HIPCHK(this, hipMemcpyAsync(d_car_sl, host.data(), sizeof(CarParams) * B_full, hipMemcpyHostToDevice, stream));
+    } else {
+        if (slot_alloc(d_track_sl, 1)) { (void)hipGetLastError(); err = msg; return MPOPIS_ERR_HIP; }
+        const std::vector<Track> host((size_t)B_full, env.track);
+        HIPCHK(this, hipMemcpyAsync(d_track_sl, host.data(), sizeof(Track) * B_full, hipMemcpyHostToDevice, stream));
+        track_sl_lds_all = track_lds_bytes(env.track.P, env.track.nbrw, true); track_sl_lds_ring = track_lds_bytes(env.track.P, env.track.nbrw, false);
+    }
+    HIPCHK(this, hipStreamSynchronize(stream));
+    return MPOPIS_OK;
+}
+
+// One parameter vector per slot.  A setup call: the [B] struct array is written only after everything queued has finished (the rollout kernels read
+// it through the constant address space).  Everything is checked and formed on the host first, so a refused call changes nothing.
+int mpopis_set_env_params_slots(mpopis_handle* h, const double* p, int32_t n) {
+    if (!h) return MPOPIS_ERR_ARG;
+    if (!p) { h->err = "mpopis_set_env_params_slots: p is NULL"; return MPOPIS_ERR_ARG; }
+    const int kind = h->env.kind, B = h->B_full;
+    if (kind == MPOPIS_ENV_CUSTOM) {
+        h->err = "mpopis_set_env_params_slots: not for a custom handle (per-slot data of a custom env goes through mpopis_set_env_table(..., per_slot))";
+        return MPOPIS_ERR_ARG;
+    }
+    const int want = kind == MPOPIS_ENV_CAR ? MPOPIS_CAR_NPARAMS : kind == MPOPIS_ENV_CARTPOLE ? MPOPIS_CARTPOLE_NPARAMS : MPOPIS_MOUNTAINCAR_NPARAMS;
+    if (n != want) {
+        h->err = "mpopis_set_env_params_slots: this env expects " + std::to_string(want) + " parameters per slot, got n = " + std::to_string(n);
+        return MPOPIS_ERR_ARG;
+    }
+    if (const int rc = quiesce(h)) return rc;
+    auto upload = [&](auto*& dst, auto make) -> int {
+        std::vector<std::remove_reference_t<decltype(*dst)>> host((size_t)B);
+        for (int b = 0; b < B; ++b) host[b] = make(p + (size_t)b * n);
+        if (h->slot_alloc(dst, 1)) { (void)hipGetLastError(); h->err = "mpopis_set_env_params_slots: hipMalloc of the per-slot parameter array failed"; return MPOPIS_ERR_HIP; }
+        HIPCHK(h, hipMemcpyAsync(dst, host.data(), sizeof(host[0]) * B, hipMemcpyHostToDevice, h->stream));      // (behind the buffer's zero-fill)
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return MPOPIS_OK;
+    };
+    int rc;
+    if (kind == MPOPIS_ENV_CAR) rc = upload(h->d_car_sl, [](const double* q) { return make_car_params(q); });
+    else if (kind == MPOPIS_ENV_CARTPOLE) rc = upload(h->d_cp_sl, [](const double* q) { return make_cp_params(q); });
+    else rc = upload(h->d_mc_sl, [](const double* q) { return make_mc_params(q); });
+    if (rc) return rc;
+    const bool was = h->env_params_slots_on;
+    h->env_params_slots_on = true;
+    if ((rc = h->sync_slot_env())) h->env_params_slots_on = was;
+    return rc;
 }
 
 // The table of a caller's env (MPOPIS_DEFINE_ENV_TABLE).  A setup call: it waits for everything the handle has queued, on the part-chain streams
@@ -496,9 +556,8 @@ int mpopis_set_env_table(mpopis_handle* h, const double* data, int64_t n, int32_
     return MPOPIS_OK;
 }
 
-int mpopis_set_track(mpopis_handle* h, const double* x, const double* y, const double* w, int32_t P) {
-    if (!h || !x || !y || !w || P < 2 || P > mpopis::kMaxTrackPoints) { if (h) h->err = "bad track (need 2 <= P <= 2048 points)"; return MPOPIS_ERR_ARG; }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
+// one track to the device: x, y, w, |q|^2, the neighbour tables and the ring table with its certificates; *out = its descriptor
+static int upload_track(mpopis_handle* h, const double* x, const double* y, const double* w, int32_t P, Track* out) {
     double* d = nullptr;
     if (h->shared_alloc(d, (size_t)4 * P)) return MPOPIS_ERR_HIP;
     std::vector<double> n2(P);
@@ -522,8 +581,60 @@ int mpopis_set_track(mpopis_handle* h, const double* x, const double* y, const d
     HIPCHK(h, hipMemcpyAsync(dring, ring.data(), sizeof(double) * ring.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(dring + ring.size(), cert.data(), sizeof(double) * cert.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, wait_stream(h->stream));
-    h->env.track = Track{d, d + P, d + 2 * P, d + 3 * P, P, dni, dnd, W, dring, dring + ring.size()};
+    *out = Track{d, d + P, d + 2 * P, d + 3 * P, P, dni, dnd, W, dring, dring + ring.size()};
     return MPOPIS_OK;
+}
+
+int mpopis_set_track(mpopis_handle* h, const double* x, const double* y, const double* w, int32_t P) {
+    if (!h || !x || !y || !w || P < 2 || P > mpopis::kMaxTrackPoints) { if (h) h->err = "bad track (need 2 <= P <= 2048 points)"; return MPOPIS_ERR_ARG; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    Track tk;
+    if (const int rc = upload_track(h, x, y, w, P, &tk)) return rc;
+    if (h->env_params_slots_on || h->track_slots_on) {         // (after mpopis_set_tracks: back to one shared track)
+        if (const int rc = quiesce(h)) return rc;
+        h->env.track = tk;
+        h->track_slots_on = false;
+        return h->sync_slot_env();
+    }
+    h->env.track = tk;
+    return MPOPIS_OK;
+}
+
+// ntracks tracks, each uploaded once; slot b's descriptor is a copy of that of track track_of_slot[b].  Like mpopis_set_track, every call uploads
+// into fresh buffers that the handle keeps until mpopis_destroy (a launch still queued may read the old ones): ~170 B per track point per call.  A setup call like mpopis_set_env_params_slots;
+// the handle changes only once every track is on the device.
+int mpopis_set_tracks(mpopis_handle* h, int32_t ntracks, const int32_t* P, const double* x, const double* y, const double* w, const int32_t* track_of_slot) {
+    if (!h) return MPOPIS_ERR_ARG;
+    const int B = h->B_full;
+    if (h->env.kind != MPOPIS_ENV_CAR) { h->err = "mpopis_set_tracks: not a car handle (only the car env drives on a track)"; return MPOPIS_ERR_ARG; }
+    if (!P || !x || !y || !w) { h->err = "mpopis_set_tracks: P, x, y or w is NULL"; return MPOPIS_ERR_ARG; }
+    if (ntracks < 1) { h->err = "mpopis_set_tracks: need at least one track"; return MPOPIS_ERR_ARG; }
+    if (!track_of_slot && ntracks != B) { h->err = "mpopis_set_tracks: without track_of_slot there must be one track per slot (" + std::to_string(B) + "), got " + std::to_string(ntracks); return MPOPIS_ERR_ARG; }
+    for (int i = 0; i < ntracks; ++i)
+        if (P[i] < 2 || P[i] > mpopis::kMaxTrackPoints) { h->err = "mpopis_set_tracks: bad track " + std::to_string(i) + " (need 2 <= P <= 2048 points, got " + std::to_string(P[i]) + ")"; return MPOPIS_ERR_ARG; }
+    if (track_of_slot)
+        for (int b = 0; b < B; ++b)
+            if (track_of_slot[b] < 0 || track_of_slot[b] >= ntracks) { h->err = "mpopis_set_tracks: track_of_slot of slot " + std::to_string(b) + " is " + std::to_string(track_of_slot[b]) + " (need 0.." + std::to_string(ntracks - 1) + ")"; return MPOPIS_ERR_ARG; }
+    if (const int rc = quiesce(h)) return rc;
+    std::vector<Track> tks((size_t)ntracks);
+    size_t off = 0, lds_all = 0, lds_ring = 0;
+    for (int i = 0; i < ntracks; ++i) {
+        if (const int rc = upload_track(h, x + off, y + off, w + off, P[i], &tks[i])) return rc;
+        off += (size_t)P[i];
+    }
+    std::vector<Track> host((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        host[b] = tks[track_of_slot ? track_of_slot[b] : b];
+        lds_all = std::max(lds_all, track_lds_bytes(host[b].P, host[b].nbrw, true));
+        lds_ring = std::max(lds_ring, track_lds_bytes(host[b].P, host[b].nbrw, false));
+    }
+    // both arrays are allocated before either is written: past this point nothing can fail but a copy on a quiesced stream
+    if (h->slot_alloc(h->d_track_sl, 1) || h->slot_alloc(h->d_car_sl, 1)) { (void)hipGetLastError(); h->err = "mpopis_set_tracks: hipMalloc of the per-slot env arrays failed"; return MPOPIS_ERR_HIP; }
+    HIPCHK(h, hipMemcpyAsync(h->d_track_sl, host.data(), sizeof(Track) * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->track_sl_lds_all = lds_all; h->track_sl_lds_ring = lds_ring;
+    h->track_slots_on = true;
+    return h->sync_slot_env();
 }
 
 int mpopis_set_action_bounds(mpopis_handle* h, const double* lo, const double* hi) {
@@ -813,7 +924,7 @@ int mpopis_env_step(mpopis_handle* h, const double* action, double* reward) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpyAsync(h->d_control, action, sizeof(double) * h->B * h->as, hipMemcpyHostToDevice, h->stream));
     fill_i32(h->d_status, 0, h->B, h->stream);
-    HIPCHK(h, launch_env_step(h->env, h->d_x, h->d_t, h->d_done, h->d_control, h->d_reward, h->d_status, nullptr, h->B, h->stream));
+    HIPCHK(h, launch_env_step(h->env, h->d_x, h->d_t, h->d_done, h->d_control, h->d_reward, h->d_status, nullptr, h->B, h->stream, h->slot_env()));
     if (reward) HIPCHK(h, hipMemcpyAsync(reward, h->d_reward, sizeof(double) * h->B, hipMemcpyDeviceToHost, h->stream));
     return sync_status(h);
 }
@@ -824,7 +935,7 @@ int mpopis_env_query(mpopis_handle* h, double* reward, int32_t* within, double* 
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, NC = std::max(1, h->env.ncars);
     if (h->slot_alloc(h->d_qdist, NC) || h->slot_alloc(h->d_qbeta, NC) || h->slot_alloc(h->d_qwithin, 1)) return MPOPIS_ERR_HIP;
-    HIPCHK(h, launch_env_query(h->env, h->d_x, h->d_t, h->d_done, h->d_reward, h->d_qwithin, h->d_qdist, h->d_qbeta, B, h->stream));
+    HIPCHK(h, launch_env_query(h->env, h->d_x, h->d_t, h->d_done, h->d_reward, h->d_qwithin, h->d_qdist, h->d_qbeta, B, h->stream, h->slot_env()));
     if (reward) HIPCHK(h, hipMemcpyAsync(reward, h->d_reward, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
     if (within) HIPCHK(h, hipMemcpyAsync(within, h->d_qwithin, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
     if (dist) HIPCHK(h, hipMemcpyAsync(dist, h->d_qdist, sizeof(double) * B * NC, hipMemcpyDeviceToHost, h->stream));
@@ -1050,7 +1161,7 @@ int mpopis_bench_policy_steps(mpopis_handle* h, int32_t steps, double* ms, doubl
 
 // ---- launch sequences -----------------------------------------------------------------------------
 void mpopis_handle::prepare_state() {
-    if (env.kind == MPOPIS_ENV_CAR) launch_extend_state(d_x, d_xext, B, env.ncars, stream, env.track);
+    if (env.kind == MPOPIS_ENV_CAR) launch_extend_state(d_x, d_xext, B, env.ncars, stream, env.track, slot_tracks());
 }
 
 void mpopis_handle::rollout(const double* Ucur, const double* Uorig, const double* gvec, const int* act, int* iters, int iter_n) {
@@ -1060,6 +1171,7 @@ void mpopis_handle::rollout(const double* Ucur, const double* Uorig, const doubl
     a.cost = d_cost; a.traj = d_traj; a.active = act; a.iters = iters; a.iter_n = iter_n;
     a.cmin = weights_in_moments ? d_cmin : nullptr; a.status = weights_in_moments ? d_status : nullptr;
     a.share = coop_share;
+    a.senv = slot_env();
     time_begin(0);
     hipError_t custom_err = hipSuccess;
     if (!launch_rollout(a, stream, &custom_err) && launch_err.empty())
@@ -1255,7 +1367,7 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
     const bool sigma_fixed = (pol == MPOPIS_POL_MPPI || pol == MPOPIS_POL_GMPPI || pol == MPOPIS_POL_IMPPI || pol == MPOPIS_POL_MUAISMPPI);
     // status / active / iters reset, U_orig = pol.U (d_Uin keeps U_orig; d_Ucur is the rebinding pol.U inside the loop), extended start states
     launch_step_begin(status_sticky ? nullptr : d_status, d_active, alive_gate, d_iters, d_U, d_Uin, d_Ucur, B, cs,
-                      env.kind == MPOPIS_ENV_CAR ? d_x : nullptr, d_xext, env.ncars, stream, weights_in_moments ? d_cmin : nullptr, env.track, d_iters_acc);
+                      env.kind == MPOPIS_ENV_CAR ? d_x : nullptr, d_xext, env.ncars, stream, weights_in_moments ? d_cmin : nullptr, env.track, d_iters_acc, slot_tracks());
     if (!sigma_fixed) {                                                                                                          // Σ′ = pol.Σ
         if (S0stride) copy_f64(S0.Sigma, d_Sig, (size_t)B * nn, stream);                                                         // (each slot's own)
         else hipLaunchKernelGGL(k_bcast_f64, dim3((nn + 255) / 256), dim3(256), 0, stream, S0.Sigma, d_Sig, nn, B);

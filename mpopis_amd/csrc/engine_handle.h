@@ -79,6 +79,24 @@ struct mpopis_handle {
     mpopis::SlotVal sv_sigma() const { return {cfg.cma_sigma, d_sl_sigma}; }
     mpopis::SlotVal sv_nes_a() const { return {-cfg.cma_sigma / ((double)K * K), d_sl_nes_a}; }
     mpopis::SlotVal sv_nes_u() const { return {cfg.cma_sigma / K, d_sl_nes_u}; }
+    // Per-slot env (mpopis_set_env_params_slots / mpopis_set_tracks).  One [B] array of ready-made parameter structs -- the one of the handle's env
+    // kind -- and one of track descriptors, each allocated by the first call of its setter and moved with the slot views; the tracks themselves
+    // are shared buffers the descriptors point into.  *_on: the array is IN FORCE (off again after mpopis_set_env_params / mpopis_set_track).
+    // On a car handle with exactly one of the two in force the other array holds B copies of the shared value (sync_slot_env, called by the four
+    // setters): the rollout kernels' per-slot form reads both.
+    mpopis::CarParams* d_car_sl = nullptr; mpopis::McParams* d_mc_sl = nullptr; mpopis::CpParams* d_cp_sl = nullptr;
+    mpopis::Track* d_track_sl = nullptr;
+    bool env_params_slots_on = false, track_slots_on = false;
+    size_t track_sl_lds_all = 0, track_sl_lds_ring = 0;          // track_lds_bytes of the largest per-slot track (rollout_form goes by it)
+    mpopis::SlotEnv slot_env() const {
+        mpopis::SlotEnv se;
+        const bool car_any = env.kind == MPOPIS_ENV_CAR && (env_params_slots_on || track_slots_on);
+        if (env_params_slots_on || car_any) { se.car = d_car_sl; se.mc = d_mc_sl; se.cp = d_cp_sl; }
+        if (track_slots_on || car_any) { se.track = d_track_sl; se.lds_all = track_sl_lds_all; se.lds_ring = track_sl_lds_ring; }
+        return se;
+    }
+    const mpopis::Track* slot_tracks() const { return slot_env().track; }
+    int sync_slot_env();                                       // engine_api.hip; sets err
     bool fold_weights_cfg = false;                // what weights_in_moments is while λ_ais is the config's scalar
     // samples / costs / weights
     double *d_Z = nullptr, *d_E = nullptr, *d_Zin = nullptr, *d_cost = nullptr, *d_w = nullptr;
@@ -168,7 +186,7 @@ struct mpopis_handle {
     int step_enqueue_view(bool injected, hipEvent_t wait_first, hipEvent_t record_after_first_sampler);
     void shift_slots(ptrdiff_t db);                           // move every per-slot device pointer by db slots (slot views)
     // the checks and messages several entry points share
-    bool track_missing() { if (env.kind != MPOPIS_ENV_CAR || env.track.P != 0) return false; err = "track not set"; return true; }
+    bool track_missing() { if (env.kind != MPOPIS_ENV_CAR || env.track.P != 0 || track_slots_on) return false; err = "track not set"; return true; }
     int report_status(int st) {                               // the message that goes with the worst per-slot status of a call; returns st
         if (st == MPOPIS_ERR_NOT_PD) err = "PosDefException: proposal covariance is not positive definite";
         else if (st == MPOPIS_ERR_ACTION) err = "Action is not in action space (non-finite control/cost)";

@@ -32,9 +32,10 @@ __global__ void k_harness_init(double* hs, int* alive, int B) {
 struct StateNoise { double sx, sy, spsi; const uint64_t* seeds; const double* rng_tab; };
 __global__ void k_harness_update(EnvDesc env, double* x, const int* done_env, const double* reward, const int* iters,
                                  double* hs, int* alive, const double* control, double* actlog, int step, int num_steps, int laps, int K, int B,
-                                 StateNoise nz) {
+                                 StateNoise nz, SlotEnv senv) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B || !alive[b]) return;
+    slot_env_into(env, senv, b);                                               // blim and within_track of the slot's own car and track
     double* h = hs + (size_t)b * kH_N;
     if (nz.seeds && env.kind == MPOPIS_ENV_CAR && env.ncars == 1) {            // :224-236 (sim_type == :cr only), after reward(env)
         double z0, z1, z2, z3;
@@ -120,11 +121,11 @@ int mpopis_handle::run_trials(int num_steps, int laps, double* records, double* 
         if (!chain_np) chains_fork();
         alive_gate = d_alive;
         int rc = chains_step(false, [&] {                       // (runs once per part, with B / stream / the slot pointers narrowed to that part)
-            const hipError_t e = launch_env_step(env, d_x, d_t, d_done, d_control, d_reward, d_status, d_alive, B, stream);
+            const hipError_t e = launch_env_step(env, d_x, d_t, d_done, d_control, d_reward, d_status, d_alive, B, stream, slot_env());
             if (e != hipSuccess && launch_err.empty()) launch_err = std::string("env step: launching the custom env's kernel failed: ") + hipGetErrorString(e);
             hipLaunchKernelGGL(k_harness_update, dim3((B + 63) / 64), dim3(64), 0, stream, env, d_x, d_done, d_reward, d_iters, d_hs, d_alive,
                                d_control, d_actlog, s, num_steps, laps, K, B,
-                               StateNoise{noise_sx, noise_sy, noise_spsi, noisy ? d_seeds : (const uint64_t*)nullptr, d_rng_tab});
+                               StateNoise{noise_sx, noise_sy, noise_spsi, noisy ? d_seeds : (const uint64_t*)nullptr, d_rng_tab}, slot_env());
         });
         alive_gate = nullptr;
         if (rc) { chains_join(); status_sticky = false; return rc; }

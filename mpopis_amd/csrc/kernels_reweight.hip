@@ -184,9 +184,10 @@ void launch_transpose_out(const double* src, const double* shiftA, const double*
 
 // env(action); reward(env) for the resident real envs (one workgroup per slot, lane c = car c)
 __global__ void __launch_bounds__(64) k_env_step(EnvDesc env, double* x, int* t, int* done, const double* action,
-                                                 double* reward, int* status, const int* alive) {
+                                                 double* reward, int* status, const int* alive, SlotEnv senv) {
     const int b = blockIdx.x, c = threadIdx.x;
     if (alive && !alive[b]) return;
+    slot_env_into(env, senv, b);
     __shared__ double srew[kMaxCars];
     if (env.kind != MPOPIS_ENV_CAR) {
         if (c == 0) {
@@ -231,9 +232,10 @@ __global__ void __launch_bounds__(64) k_env_step(EnvDesc env, double* x, int* t,
     }
 }
 // reward(env) / within_track / β of the resident state, no step
-__global__ void __launch_bounds__(64) k_env_query(EnvDesc env, const double* x, const int* done, double* reward, int* within, double* dist, double* beta) {
+__global__ void __launch_bounds__(64) k_env_query(EnvDesc env, const double* x, const int* done, double* reward, int* within, double* dist, double* beta, SlotEnv senv) {
     const int b = blockIdx.x;
     if (threadIdx.x != 0) return;
+    slot_env_into(env, senv, b);
     if (env.kind != MPOPIS_ENV_CAR) {
         if (reward) reward[b] = simple_env_reward(env, x + (size_t)b * env.ss, done[b]);
         if (within) within[b] = 1;
@@ -275,15 +277,15 @@ static hipError_t launch_custom_env_kernel(hipFunction_t fn, const EnvDesc& env,
     return hipModuleLaunchKernel(fn, (B + 63) / 64, 1, 1, 64, 1, 1, 0, s, params, nullptr);
 }
 
-hipError_t launch_env_query(const EnvDesc& env, const double* x, const int* t, const int* done, double* reward, int* within, double* dist, double* beta, int B, hipStream_t s) {
+hipError_t launch_env_query(const EnvDesc& env, const double* x, const int* t, const int* done, double* reward, int* within, double* dist, double* beta, int B, hipStream_t s, const SlotEnv& senv) {
     if (env.kind == MPOPIS_ENV_CUSTOM) return launch_custom_env_kernel(env.custom->query, env, x, t, done, nullptr, reward, nullptr, nullptr, within, B, s);
-    hipLaunchKernelGGL(k_env_query, dim3(B), dim3(64), 0, s, env, x, done, reward, within, dist, beta);
+    hipLaunchKernelGGL(k_env_query, dim3(B), dim3(64), 0, s, env, x, done, reward, within, dist, beta, senv);
     return hipSuccess;
 }
 
-hipError_t launch_env_step(const EnvDesc& env, double* x, int* t, int* done, const double* action, double* reward, int* status, const int* alive, int B, hipStream_t s) {
+hipError_t launch_env_step(const EnvDesc& env, double* x, int* t, int* done, const double* action, double* reward, int* status, const int* alive, int B, hipStream_t s, const SlotEnv& senv) {
     if (env.kind == MPOPIS_ENV_CUSTOM) return launch_custom_env_kernel(env.custom->step, env, x, t, done, action, reward, status, alive, nullptr, B, s);
-    hipLaunchKernelGGL(k_env_step, dim3(B), dim3(64), 0, s, env, x, t, done, action, reward, status, alive);
+    hipLaunchKernelGGL(k_env_step, dim3(B), dim3(64), 0, s, env, x, t, done, action, reward, status, alive, senv);
     return hipSuccess;
 }
 

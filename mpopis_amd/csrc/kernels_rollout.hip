@@ -17,9 +17,19 @@
 // Two device bodies serve 1..8 cars: rollout_one_wave (each wave integrates and rewards its samples) and rollout_two_wave (a dynamics wave hands
 // the state to a reward wave, for few rollouts).  The entry points k_rollout_car / k_rollout_car_duo (one car) and k_rollout_cars /
 // k_rollout_cars_duo (2..8 cars) are one call each into them, with their own launch bounds and occupancy.
+// The per-slot-env twins of the car kernels are compiled from this same text as a translation unit of their own,
+// kernels_rollout_slots.hip (it defines MPOPIS_ROLLOUT_SLOT_TWINS and includes this file): the kernel templates and the launcher templates are
+// shared, everything else -- the simple envs, the start-state kernels, rollout_form, launch_rollout -- exists here only.  The build stays as
+// long as its longest file that way; with both sets in one file it took twice the time.
 #include "engine.h"
 
 namespace mpopis {
+#ifdef MPOPIS_ROLLOUT_SLOT_TWINS
+constexpr bool kSlotTwins = true;
+#else
+constexpr bool kSlotTwins = false;
+#endif
+bool launch_car_rollout_slots(const RolloutArgs& a, const RolloutForm& f, hipStream_t st);      // kernels_rollout_slots.hip: the SENV instantiations
 
 // Track tables into LDS (dynamic LDS layout: ring table [(P+6)][6] + certification radii [2][P]; with ALL: + x, y, w, |q|^2 [4][P] + neighbour
 // distances [P][W+1] + neighbour indices [P][W+1]).  Returns the Track the rollout uses; the caller synchronises.
@@ -37,9 +47,6 @@ __device__ __forceinline__ Track stage_track(const Track& g, double* sh, int tid
     for (int i = tid; i < P; i += nthreads) { sh_trk[i] = g.x[i]; sh_trk[P + i] = g.y[i]; sh_trk[2 * P + i] = g.w[i]; sh_trk[3 * P + i] = g.n2[i]; }
     for (int i = tid; i < NS; i += nthreads) { sh_nd[i] = g.nbr_dist[i]; sh_ni[i] = g.nbr_idx[i]; }
     return Track{sh_trk, sh_trk + P, sh_trk + 2 * P, sh_trk + 3 * P, P, sh_ni, sh_nd, W, sh_ring, sh_cert};
-}
-inline size_t track_lds_bytes(int P, int W, bool all) {
-    return (size_t)(kRingStride * (P + 2 * kRingPad) + 2 * P) * sizeof(double) + (all ? (size_t)4 * P * sizeof(double) + (size_t)P * (W + 1) * (sizeof(double) + sizeof(int)) : 0);
 }
 
 // TLDS: every track table fits the default 64 KB of dynamic LDS (P <= 190 points: all bundled tracks).  Otherwise only the ring table of the
@@ -206,25 +213,39 @@ struct RolloutMailbox {
     }
 };
 
+// The env of slot b.  SENV (a handle after mpopis_set_env_params_slots / mpopis_set_tracks): the slot's own CarParams and Track descriptor, copied
+// from the [B] arrays at the top of the kernel through the constant address space, at an address every lane of the workgroup shares
+// (b = blockIdx.y) -- so the copies are scalar loads into SGPRs, where the shared form keeps its kernel arguments.  The setters are setup calls
+// (they wait for the handle's queued work), so nothing writes these arrays under a running kernel.  A car handle with either per-slot part
+// in force passes BOTH arrays (the other one holds copies of the shared value, mpopis_handle::sync_slot_env): choosing between an array and the
+// kernel argument here would make the address generic and the loads vector loads, 80 VGPRs of parameters.
+template <class P>
+__device__ __forceinline__ void slot_const_copy(P& dst, const P* src) {
+    typedef const P __attribute__((address_space(4))) * CP;      // the constant address space: what makes the copy scalar loads
+    __builtin_memcpy(&dst, (CP)src, sizeof(P));
+}
+
 // ---- the two bodies ----
 
 // One wave integrates and rewards S samples x NC cars; SPB sample-waves per workgroup share one LDS copy of the track tables.
 // LOG: the trajectory logger is on (a.traj != nullptr) -- only then is the heading angle psi itself tracked.
-template <int NC, int SPB, bool LOG, bool TLDS>
+template <int NC, int SPB, bool LOG, bool TLDS, bool SENV>
 __device__ __forceinline__ void rollout_one_wave(const RolloutArgs& a) {
 #ifdef MPOPIS_ROLL_PROF
     const unsigned long long prof_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
     const int b = blockIdx.y;
+    CarParams slot_car; Track slot_tk;
+    if constexpr (SENV) { slot_const_copy(slot_car, a.senv.car + b); slot_const_copy(slot_tk, a.senv.track + b); }
     if (!rollout_slot_begin(a, b)) return;
     const int g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);           // sample-wave of the workgroup
     const CarLane<NC> l(blockIdx.x * SPB + g, a.K);
     const int T = a.T;
-    const CarParams& p = a.env.car;
+    const CarParams& p = SENV ? slot_car : a.env.car;
     // stage the (wave-uniform, read-only) track in LDS: uniform-address ds_reads broadcast to all lanes
     extern __shared__ __attribute__((aligned(16))) double sh_dyn[];
     __shared__ double sh_bnd[NC][4];
-    const Track tk = stage_track<TLDS>(a.env.track, sh_dyn, threadIdx.x, 64 * SPB);
+    const Track tk = stage_track<TLDS>(SENV ? slot_tk : a.env.track, sh_dyn, threadIdx.x, 64 * SPB);
     stage_action_bounds<NC>(a.env, sh_bnd);
     __syncthreads();
     CarState s = load_start_state<NC>(a, b, l.c);
@@ -278,18 +299,20 @@ __device__ __forceinline__ void rollout_one_wave(const RolloutArgs& a) {
 // penalty: ~110 of the ~885 instructions of a one-car model step) and the pair terms, accumulates the cost and sums it over the cars.  Same
 // arithmetic in the same order as rollout_one_wave -- bit-identical costs -- with the dynamics wave's chain 11 % shorter at one car.  The reward
 // wave is ~8x faster than the dynamics wave, so the producer practically never waits for a free slot.
-template <int NC, bool TLDS>
+template <int NC, bool TLDS, bool SENV>
 __device__ __forceinline__ void rollout_two_wave(const RolloutArgs& a) {
     const int b = blockIdx.y;
+    CarParams slot_car; Track slot_tk;
+    if constexpr (SENV) { slot_const_copy(slot_car, a.senv.car + b); slot_const_copy(slot_tk, a.senv.track + b); }
     if (!rollout_slot_begin(a, b)) return;
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);        // 0: dynamics, 1: reward
     const CarLane<NC> l(blockIdx.x, a.K);
     const int T = a.T;
-    const CarParams& p = a.env.car;
+    const CarParams& p = SENV ? slot_car : a.env.car;
     extern __shared__ __attribute__((aligned(16))) double sh_dyn[];
     __shared__ double sh_bnd[NC][4];
     __shared__ RolloutMailbox mb;
-    const Track tk = stage_track<TLDS>(a.env.track, sh_dyn, threadIdx.x, 128);
+    const Track tk = stage_track<TLDS>(SENV ? slot_tk : a.env.track, sh_dyn, threadIdx.x, 128);
     stage_action_bounds<NC>(a.env, sh_bnd);
     if (threadIdx.x == 0) { mb.ready = 0; mb.done = 0; }
     __syncthreads();
@@ -323,38 +346,40 @@ __device__ __forceinline__ void rollout_two_wave(const RolloutArgs& a) {
 // ---- the entry points ----
 
 // One car (CarRacingEnv), 4 waves per SIMD
-template <int NC, int SPB, bool LOG, bool TLDS>
+template <int NC, int SPB, bool LOG, bool TLDS, bool SENV = false>
 __global__ void __launch_bounds__(64 * NC * SPB) __attribute__((amdgpu_waves_per_eu(4, 4))) k_rollout_car(RolloutArgs a) {
     static_assert(NC == 1, "multi-car envs run k_rollout_cars");
-    rollout_one_wave<NC, SPB, LOG, TLDS>(a);
+    rollout_one_wave<NC, SPB, LOG, TLDS, SENV>(a);
 }
 
 // One car, two waves: held to 128 VGPRs = 4 waves per SIMD, so two dynamics and two reward waves share a SIMD
-template <bool TLDS>
+template <bool TLDS, bool SENV = false>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4))) k_rollout_car_duo(RolloutArgs a) {
-    rollout_two_wave<1, TLDS>(a);
+    rollout_two_wave<1, TLDS, SENV>(a);
 }
 
 // NC >= 2 cars (MultiCarRacingEnv).  The launch runs it at WPE = 3 waves per SIMD: 168 VGPRs, no spills, 1411 us at 64 three-car trials,
 // against 1509 us at 4 (128 VGPRs, 33 spills).
-template <int NC, int SPB, bool LOG, int WPE, bool TLDS>
+template <int NC, int SPB, bool LOG, int WPE, bool TLDS, bool SENV = false>
 __global__ void __launch_bounds__(64 * SPB) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_rollout_cars(RolloutArgs a) {
     static_assert(NC >= 2 && NC <= kMaxCars, "2..8 cars");
-    rollout_one_wave<NC, SPB, LOG, TLDS>(a);
+    rollout_one_wave<NC, SPB, LOG, TLDS, SENV>(a);
 }
 
 // NC >= 2 cars, two waves, 3 waves per SIMD
-template <int NC, bool TLDS>
+template <int NC, bool TLDS, bool SENV = false>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) k_rollout_cars_duo(RolloutArgs a) {
     static_assert(NC >= 2 && NC <= kMaxCars, "2..8 cars");
-    rollout_two_wave<NC, TLDS>(a);
+    rollout_two_wave<NC, TLDS, SENV>(a);
 }
 
+#ifndef MPOPIS_ROLLOUT_SLOT_TWINS
 // MountainCar (ss = 2) and CartPole (ss = 4): scalar action, a handful of flops per step
-template <int SS>
+template <int SS, bool SENV = false>
 __global__ void __launch_bounds__(64) k_rollout_simple(RolloutArgs a) {
     const int b = blockIdx.y;
     if (!rollout_slot_begin(a, b)) return;
+    if constexpr (SENV) slot_env_into(a.env, a.senv, b);
     const int k = blockIdx.x * 64 + threadIdx.x;
     const int K = a.K, T = a.T;
     const bool valid = k < K;
@@ -400,22 +425,24 @@ __device__ __forceinline__ void write_xext(const double* x8, double* o, const Tr
     if (tk.P > 0) { double dist; (void)within_track(tk, c.x, c.y, &dist, &near); }
     o[12] = (double)near;
 }
-__global__ void k_extend_state(const double* x, double* xext, int n_cars_total, Track tk) {
+__global__ void k_extend_state(const double* x, double* xext, int n_cars_total, Track tk, const Track* slot_tk, int ncars) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n_cars_total) return;
+    if (slot_tk) tk = slot_tk[i / ncars];
     write_xext(x + (size_t)i * 8, xext + (size_t)i * kCarExt, tk);
 }
-void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t st, const Track& tk) {
+void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t st, const Track& tk, const Track* slot_tk) {
     const int n = B * ncars;
-    hipLaunchKernelGGL(k_extend_state, dim3((n + 63) / 64), dim3(64), 0, st, x, xext, n, tk);
+    hipLaunchKernelGGL(k_extend_state, dim3((n + 63) / 64), dim3(64), 0, st, x, xext, n, tk, slot_tk, std::max(1, ncars));
 }
 
 // Start of an MPC step, one launch instead of seven (at one trial the step is a chain of dependent launches, each boundary costs 2-4 us):
 // status = 0 (unless sticky), active = alive gate (or 1), iters = 0, U_orig = the loop's pol.U = pol.U, and the car start states extended
 // with sin/cos of psi / delta (as k_extend_state).
 __global__ void __launch_bounds__(256) k_step_begin(int* status, int* active, const int* alive, int* iters, const double* U, double* Uin, double* Ucur,
-                                                    int cs, const double* x, double* xext, int ncars, unsigned long long* cmin, Track tk, unsigned long long* iters_acc) {
+                                                    int cs, const double* x, double* xext, int ncars, unsigned long long* cmin, Track tk, unsigned long long* iters_acc, const Track* slot_tk) {
     const int b = blockIdx.x, tid = threadIdx.x;
+    if (slot_tk) tk = slot_tk[b];
     if (tid == 0) {
         if (iters_acc) iters_acc[b] += (unsigned long long)iters[b];          // the previous step's executed iterations (CE / CMA early breaks counted as run)
         if (status) status[b] = 0; active[b] = alive ? alive[b] : 1; iters[b] = 0; if (cmin) cmin[b] = ~0ull;
@@ -452,9 +479,11 @@ __global__ void __launch_bounds__(256) k_step_begin(int* status, int* active, co
     }
 }
 void launch_step_begin(int* status, int* active, const int* alive, int* iters, const double* U, double* Uin, double* Ucur, int B, int cs,
-                       const double* x, double* xext, int ncars, hipStream_t st, unsigned long long* cmin, const Track& tk, unsigned long long* iters_acc) {
-    hipLaunchKernelGGL(k_step_begin, dim3(B), dim3(256), 0, st, status, active, alive, iters, U, Uin, Ucur, cs, x, xext, ncars, cmin, tk, iters_acc);
+                       const double* x, double* xext, int ncars, hipStream_t st, unsigned long long* cmin, const Track& tk, unsigned long long* iters_acc, const Track* slot_tk) {
+    hipLaunchKernelGGL(k_step_begin, dim3(B), dim3(256), 0, st, status, active, alive, iters, U, Uin, Ucur, cs, x, xext, ncars, cmin, tk, iters_acc, slot_tk);
 }
+
+#endif      // !MPOPIS_ROLLOUT_SLOT_TWINS
 
 // Dynamic LDS a rollout kernel may request without raising its limit: the default 64 KB minus the kernels' STATIC LDS (two-wave kernels:
 // mailbox 4 KB + control-cost column 0.5 KB + flags + per-car bounds, ~4.7 KB).  Beyond it the limit is raised before the launch, once per
@@ -473,11 +502,12 @@ static void launch_rollout_kernel(dim3 grid, int block, size_t lds, hipStream_t 
 }
 
 // The one-wave form: one wave per S = 64 / NC samples, SPB waves per workgroup.  LOG: the trajectory logger; TLDS: every track table in LDS.
+// (SENV = kSlotTwins: this translation unit instantiates the shared kernels, kernels_rollout_slots.hip their per-slot-env twins)
 template <int NC, int SPB, bool LOG, bool TLDS>
 static void launch_one_wave_kernel(const RolloutArgs& a, size_t lds, hipStream_t st) {
     const dim3 grid((a.K + SPB * (64 / NC) - 1) / (SPB * (64 / NC)), a.B);
-    if constexpr (NC == 1) launch_rollout_kernel<k_rollout_car<1, SPB, LOG, TLDS>>(grid, 64 * SPB, lds, st, a);
-    else launch_rollout_kernel<k_rollout_cars<NC, SPB, LOG, 3, TLDS>>(grid, 64 * SPB, lds, st, a);
+    if constexpr (NC == 1) launch_rollout_kernel<k_rollout_car<1, SPB, LOG, TLDS, kSlotTwins>>(grid, 64 * SPB, lds, st, a);
+    else launch_rollout_kernel<k_rollout_cars<NC, SPB, LOG, 3, TLDS, kSlotTwins>>(grid, 64 * SPB, lds, st, a);
 }
 template <int NC, int SPB>
 static void launch_one_wave(const RolloutArgs& a, bool tl, size_t lds, hipStream_t st) {
@@ -488,10 +518,11 @@ static void launch_one_wave(const RolloutArgs& a, bool tl, size_t lds, hipStream
 template <int NC>
 static void launch_two_wave(const RolloutArgs& a, bool tl, size_t lds, hipStream_t st) {
     const dim3 grid((a.K + 64 / NC - 1) / (64 / NC), a.B);
-    if constexpr (NC == 1) { if (tl) launch_rollout_kernel<k_rollout_car_duo<true>>(grid, 128, lds, st, a); else launch_rollout_kernel<k_rollout_car_duo<false>>(grid, 128, lds, st, a); }
-    else { if (tl) launch_rollout_kernel<k_rollout_cars_duo<NC, true>>(grid, 128, lds, st, a); else launch_rollout_kernel<k_rollout_cars_duo<NC, false>>(grid, 128, lds, st, a); }
+    if constexpr (NC == 1) { if (tl) launch_rollout_kernel<k_rollout_car_duo<true, kSlotTwins>>(grid, 128, lds, st, a); else launch_rollout_kernel<k_rollout_car_duo<false, kSlotTwins>>(grid, 128, lds, st, a); }
+    else { if (tl) launch_rollout_kernel<k_rollout_cars_duo<NC, true, kSlotTwins>>(grid, 128, lds, st, a); else launch_rollout_kernel<k_rollout_cars_duo<NC, false, kSlotTwins>>(grid, 128, lds, st, a); }
 }
 
+#ifndef MPOPIS_ROLLOUT_SLOT_TWINS
 // The two-wave form takes launches of up to this many rollout waves per CU (all parts of a multi-stream schedule together).  Measured crossovers:
 // one car 8, i.e. 2 per SIMD (C5 shapes: 3.49 vs 3.95 ms at 32 trials, 5.36 vs 4.71 at 48); 2..8 cars (3 waves per SIMD) 5 (C4 shapes: 5.53 ->
 // 4.86 ms at one trial, 7.18 -> 6.66 at 6 (1176 waves), 7.49 -> 7.68 at 8).  MPOPIS_ROLLOUT_DUO, read once per process, replaces the limit by a
@@ -501,6 +532,8 @@ static long long rollout_duo_max_waves(int ncars) {
     static const int env_duo = [] { const char* e = getenv("MPOPIS_ROLLOUT_DUO"); return e ? atoi(e) : -1; }();
     return env_duo >= 0 ? env_duo : (long long)(ncars == 1 ? kDuoCarWaves : kDuoCarsWaves) * coop_max_workgroups();
 }
+
+#endif
 
 // NC cars (compile-time dispatch over 1..kMaxCars): the body rollout_form chose.  False: no kernel for this car count.
 template <int NC = 1>
@@ -515,6 +548,9 @@ static bool launch_car_rollout(const RolloutArgs& a, const RolloutForm& f, hipSt
     return true;
 }
 
+#ifdef MPOPIS_ROLLOUT_SLOT_TWINS
+bool launch_car_rollout_slots(const RolloutArgs& a, const RolloutForm& f, hipStream_t st) { return launch_car_rollout(a, f, st); }
+#else
 // A caller's env (include/mpopis_env.h): the rollout kernel of its code object, same grid as k_rollout_simple.  The built-in kernels treat
 // every kind that is not the car as one of the two simple envs, so a custom handle must never reach them.
 // An env with a table: four-wave workgroups; a table the code object's LDS kernel can stage goes there with ntab * 8 bytes of dynamic LDS (a small
@@ -562,11 +598,15 @@ RolloutForm rollout_form(const RolloutArgs& a) {
     const int P = a.env.track.P, W = a.env.track.nbrw, NC = a.env.ncars;
     // every table in LDS when that fits the default 64 KB (all bundled tracks: 48-60 points); larger tracks (beyond 190 points; Track(infile; sample_factor = 1):
     // ~1000 points) stage the ring table only (64 P + 288 B: 128.3 KB at the 2048-point limit; the kernels' dynamic-LDS limit is raised to 144 KB once)
-    f.tlds = track_lds_bytes(P, W, true) <= kRolloutDynLdsDefault;      // (static LDS of the two-wave kernels counted: P = 221, 222 used to total 65.7-66 KB without the limit being raised)
-    f.lds = track_lds_bytes(P, W, f.tlds);
+    // Per-slot tracks: every slot of the launch runs ONE kernel, so the handle's largest track decides the placement and the LDS size (senv.lds_all /
+    // lds_ring, formed by mpopis_set_tracks); each workgroup stages its own slot's P points into it.
+    const size_t lds_all = a.senv.track ? a.senv.lds_all : track_lds_bytes(P, W, true);
+    f.tlds = lds_all <= kRolloutDynLdsDefault;      // (static LDS of the two-wave kernels counted: P = 221, 222 used to total 65.7-66 KB without the limit being raised)
+    f.lds = f.tlds ? lds_all : a.senv.track ? a.senv.lds_ring : track_lds_bytes(P, W, false);
     if (NC < 1 || NC > kMaxCars) { f.body = ROLLOUT_ONE_WAVE_SPB1; return f; }           // (no kernel: launch_rollout returns false)
     const int S = 64 / NC;
     const long long waves = (long long)a.B * ((a.K + S - 1) / S) * std::max(1, a.share);
+    // (a per-slot-env handle takes the same body as a shared one: every instantiation has its twin)
     if (!a.traj && waves <= rollout_duo_max_waves(NC)) f.body = ROLLOUT_TWO_WAVE;
     else f.body = a.K >= 1024 ? ROLLOUT_ONE_WAVE_SPB4 : ROLLOUT_ONE_WAVE_SPB1;
     return f;
@@ -576,11 +616,13 @@ bool launch_rollout(const RolloutArgs& a, hipStream_t st, hipError_t* custom_err
     const RolloutForm f = rollout_form(a);
     if (f.body == ROLLOUT_CUSTOM) return launch_custom_rollout(a, f, st, custom_err);
     if (f.body == ROLLOUT_SIMPLE2 || f.body == ROLLOUT_SIMPLE4) {
-        const auto kernel = f.body == ROLLOUT_SIMPLE4 ? k_rollout_simple<4> : k_rollout_simple<2>;
+        const auto kernel = a.senv.mc || a.senv.cp ? (f.body == ROLLOUT_SIMPLE4 ? k_rollout_simple<4, true> : k_rollout_simple<2, true>)
+                                                   : (f.body == ROLLOUT_SIMPLE4 ? k_rollout_simple<4> : k_rollout_simple<2>);
         hipLaunchKernelGGL(kernel, dim3((a.K + 63) / 64, a.B), dim3(64), 0, st, a);
         return true;
     }
-    return launch_car_rollout(a, f, st);
+    return a.senv.car && a.senv.track ? launch_car_rollout_slots(a, f, st) : launch_car_rollout(a, f, st);
 }
+#endif      // !MPOPIS_ROLLOUT_SLOT_TWINS
 
 }  // namespace mpopis

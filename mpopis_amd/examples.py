@@ -8,7 +8,7 @@ import time
 import warnings
 import numpy as np
 
-from .engine import Engine
+from .engine import Engine, default_track
 from ._lib import MPOPISError, ERR_ARG, RECORD_LEN
 
 
@@ -95,6 +95,55 @@ def split_per_trial(value, num_trials, rank=0, world=1, cov=False):
     return None, a[[k - 1 for k in shard_trials(num_trials, rank, world)]]
 
 
+def _is_track_triple(t):
+    """(x, y, w): three 1-D coordinate arrays of one length (at least 2 points)."""
+    if isinstance(t, str) or not hasattr(t, "__len__") or len(t) != 3 or any(isinstance(v, str) for v in t):
+        return False
+    try:
+        arrs = [np.asarray(v, dtype=np.float64) for v in t]
+    except (TypeError, ValueError):
+        return False
+    return all(a.ndim == 1 for a in arrs) and arrs[0].size == arrs[1].size == arrs[2].size >= 2
+
+
+def split_tracks_per_trial(track, num_trials, rank=0, world=1):
+    """What one rank passes for the `track` keyword.  Returns (shared, per_slot), one of them None: a bundled name or one (x, y, w) triple
+    comes back as `shared`; a sequence of num_trials names or triples gives trial k (1-based) entry k - 1, and `per_slot` is
+    (tracks, track_of_slot) for Engine.set_tracks -- the distinct entries among this rank's trials (shard_trials) in order of first use, equal
+    entries (the same name, or triples with the same numbers) once, and for every slot of the rank the index of its track."""
+    if isinstance(track, str) or _is_track_triple(track):
+        return track, None
+    if not hasattr(track, "__len__") or len(track) != num_trials or not all(isinstance(t, str) or _is_track_triple(t) for t in track):
+        raise ValueError("track: a bundled name, one (x, y, w) triple of equal-length 1-D arrays, or a sequence of one of either per trial (%d)" % num_trials)
+    tracks, index, track_of_slot = [], {}, []
+    for k in shard_trials(num_trials, rank, world):
+        t = track[k - 1]
+        key = ("name", t) if isinstance(t, str) else ("xyw",) + tuple(np.asarray(v, dtype=np.float64).tobytes() for v in t)
+        if key not in index:
+            index[key] = len(tracks)
+            tracks.append(t)
+        track_of_slot.append(index[key])
+    return None, (tracks, track_of_slot)
+
+
+def split_env_params_per_trial(value, n, num_trials, rank=0, world=1):
+    """What one rank passes for `car_params` / `env_params`.  Returns (shared, per_slot), one of them None (both for value None = the env's
+    defaults): a vector of n values (include/mpopis.h lists them per env kind) is `shared`; an array of shape (num_trials, n) gives trial k
+    (1-based) row k - 1, and `per_slot` holds the rows of this rank's trials (shard_trials) in slot order, for Engine.set_env_params_slots."""
+    if value is None:
+        return None, None
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 1 and a.size == n:
+        return a, None
+    if a.ndim != 2 or a.shape != (num_trials, n):
+        raise ValueError("env parameters: %d values, or one row of %d per trial (%d), got shape %s" % (n, n, num_trials, a.shape))
+    return None, a[[k - 1 for k in shard_trials(num_trials, rank, world)]]
+
+
+def _resolve_track(t):
+    return default_track(name=t) if isinstance(t, str) else tuple(np.asarray(v, dtype=np.float64) for v in t)
+
+
 def _apply_per_trial(eng, per, cov_slots, policy):
     """Engine.set_slot_hyper / set_Sigma_slots from the per_slot halves of split_per_trial (None: that keyword is shared)."""
     if any(v is not None for v in per.values()):
@@ -107,12 +156,15 @@ def _apply_per_trial(eng, per, cov_slots, policy):
 def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="cemppi", laps=2, num_samples=150, horizon=50,
                         λ=10.0, α=1.0, U0=None, cov_mat=None, ais_its=10, λ_ais=20.0, ce_elite_threshold=0.8, ce_Σ_est="ss",
                         cma_σ=0.75, cma_elite_threshold=0.8, state_x_sigma=0.0, state_y_sigma=0.0, state_ψ_sigma=0.0,
-                        seed=None, log_runs=True, device=0, dist=None, quiet=False):
+                        seed=None, log_runs=True, device=0, dist=None, quiet=False, track="curve", car_params=None):
     """Returns (records, summary) on rank 0 (None elsewhere).  Differences from the reference harness, all
     forced by the platform: plotting/GIF options are not offered (out of scope); the state noise (single car only,
     car_example.jl:224-236) is drawn from the trial's device stream instead of the env's MersenneTwister.
     λ, α, λ_ais and cma_σ also take a sequence of num_trials values, and cov_mat a sequence of num_trials vectors or matrices
     (split_per_trial): trial k runs with entry k - 1, all trials of a rank still in one resident batch -- a hyper-parameter sweep in one call.
+    track: a bundled name (engine.BUNDLED_TRACKS) or an (x, y, w) triple, or a sequence of num_trials of either -- a policy over several tracks
+    in one resident batch, every distinct track uploaded once (split_tracks_per_trial).  car_params: the 20 values of CarRacingEnvParams + dt, δt
+    (include/mpopis.h), or (num_trials, 20) for one vector per trial (split_env_params_per_trial).
     ce_Σ_est defaults to :ss like the reference (car_example.jl:66); :mle is the other supported estimator."""
     pt = str(policy_type).lstrip(":")
     rank = dist.get_rank() if (dist is not None and dist.is_initialized()) else 0
@@ -131,15 +183,22 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
     # (the handle's own scalar of a per-trial keyword is never in force: trial 1's entry stands in for it at create)
     λ, α, λ_ais, cma_σ = [v if split[k][1] is None else float(np.asarray(v, dtype=np.float64)[0]) for k, v in kw.items()]
     cov_shared, cov_slots = split_per_trial(cov_mat, num_trials, rank, world, cov=True)
+    trk_shared, trk_slots = split_tracks_per_trial(track, num_trials, rank, world)
+    par_shared, par_slots = split_env_params_per_trial(car_params, 20, num_trials, rank, world)
     t0 = time.time()
     # every rank keeps a handle (even with no trials: it takes part in the collective); all of a rank's trials
     # k0, k0+G, ... live in ONE resident batch, slot i seeded like the reference's trial k_i: seed!(pol, seed + k) (:187-188)
     eng = Engine("car", num_cars, pt, num_samples, horizon, batch=max(len(mine), 1), lam=λ, alpha=α, ais_its=ais_its, lam_ais=λ_ais,
                  elite_threshold=(cma_elite_threshold if pt == "cmamppi" else ce_elite_threshold), sigma_est=str(ce_Σ_est).lstrip(":"),
-                 cma_sigma=cma_σ, seed=seed, device=device, cov=cov_shared, U0=U0)
+                 cma_sigma=cma_σ, seed=seed, device=device, cov=cov_shared, U0=U0,
+                 track=None if trk_shared is None else _resolve_track(trk_shared), env_params=par_shared)
     r = np.zeros((0, RECORD_LEN))
     if mine:
         _apply_per_trial(eng, {k: v[1] for k, v in split.items()}, cov_slots, pt)
+        if trk_slots is not None:
+            eng.set_tracks([_resolve_track(t) for t in trk_slots[0]], trk_slots[1])
+        if par_slots is not None:
+            eng.set_env_params_slots(par_slots)
         eng.seed_slots([seed + k for k in mine])
         eng.set_state_noise(state_x_sigma, state_y_sigma, state_ψ_sigma)
         r = eng.run_trials(num_steps, laps)
@@ -181,8 +240,9 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
 
 def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cemppi", num_samples=20, horizon=15, λ=0.1, α=1.0, U0=(0.0,),
                          cov_mat=(1.5,), ais_its=5, λ_ais=0.1, ce_elite_threshold=0.8, ce_Σ_est="mle", cma_σ=0.75,
-                         cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False):
+                         cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None):
     pt = str(policy_type).lstrip(":")
+    par_shared, par_slots = split_env_params_per_trial(env_params, 11 if env_kind == "cartpole" else 8, num_trials)
     if seed is None:
         seed = int(np.random.default_rng().integers(1, 10 ** 10))
     kw = {"λ": λ, "α": α, "λ_ais": λ_ais, "cma_σ": cma_σ}
@@ -192,8 +252,10 @@ def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cem
     eng = Engine(env_kind, 0, pt, num_samples, horizon, batch=num_trials, lam=λ, alpha=α, ais_its=ais_its, lam_ais=λ_ais,
                  elite_threshold=(cma_elite_threshold if pt == "cmamppi" else ce_elite_threshold), sigma_est=str(ce_Σ_est).lstrip(":"),
                  cma_sigma=cma_σ, seed=seed, device=device, cov=None if cov_shared is None else np.asarray(cov_shared, dtype=np.float64),
-                 U0=np.asarray(U0, dtype=np.float64))
+                 U0=np.asarray(U0, dtype=np.float64), env_params=par_shared)
     _apply_per_trial(eng, {k: v[1] for k, v in split.items()}, cov_slots, pt)
+    if par_slots is not None:
+        eng.set_env_params_slots(par_slots)
     if x0 is not None:
         eng.set_state(np.asarray(x0, dtype=np.float64).reshape(num_trials, ss))
     t0 = time.time()
@@ -214,12 +276,13 @@ def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cem
 
 _SIMPLE_KW = dict(num_trials=1, num_steps=200, policy_type="cemppi", num_samples=20, horizon=15, λ=0.1, α=1.0, U0=(0.0,),
                   cov_mat=(1.5,), ais_its=5, λ_ais=0.1, ce_elite_threshold=0.8, ce_Σ_est="mle", cma_σ=0.75,
-                  cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False)
+                  cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None)
 
 
 def simulate_mountaincar(**kw):
     """mountaincar_example.jl:49-207 (same keyword arguments and defaults); x0: per-trial start positions
-    (the reference draws x ~ U(-0.6,-0.4) from an unseeded RNG; default here -0.5)."""
+    (the reference draws x ~ U(-0.6,-0.4) from an unseeded RNG; default here -0.5).  env_params: the 8 values include/mpopis.h lists for
+    MountainCar, or (num_trials, 8) for one vector per trial."""
     a = dict(_SIMPLE_KW); _check_kw(a, kw); a.update(kw)
     if a["x0"] is not None:
         x = np.asarray(a["x0"], dtype=np.float64).reshape(a["num_trials"])
@@ -230,7 +293,8 @@ def simulate_mountaincar(**kw):
 def simulate_cartpole(**kw):
     """cartpole_example.jl:8-190 (same keyword arguments and defaults); x0: (num_trials, 4) start states
     [x, xdot, theta, thetadot].  The reference draws 0.1*rand(4) - 0.05 from an unseeded MersenneTwister (:111);
-    default here: the same box drawn from numpy's default_rng(seed + k)."""
+    default here: the same box drawn from numpy's default_rng(seed + k).  env_params: the 11 values include/mpopis.h lists for CartPole, or
+    (num_trials, 11) for one vector per trial."""
     a = dict(_SIMPLE_KW); _check_kw(a, kw); a.update(kw)
     if a["seed"] is None:
         a["seed"] = int(np.random.default_rng().integers(1, 10 ** 10))
