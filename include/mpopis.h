@@ -67,7 +67,11 @@ extern "C" {
  *    Later gained TWO more entry points, mpopis_set_env_params_slots and mpopis_set_tracks: the parameter vector of the built-in envs and the
  *    track of the car env per trial slot, so that one resident batch can hold a policy's trials on several tracks or a robustness study over
  *    car parameters.  mpopis_config and every other entry point are unchanged, and a handle that never calls them runs what it ran before; a
- *    library that predates them does not export the symbols, which is how a caller detects support. */
+ *    library that predates them does not export the symbols, which is how a caller detects support.
+ *    Later gained ONE more entry point, mpopis_get_plan: the control sequence the last policy step chose, the states it predicts, and the step's
+ *    highest-weight sample rollouts, read out on request from what is still resident after the step.  mpopis_config and every other entry point
+ *    are unchanged, and a handle that never calls it allocates and launches nothing new; a library that predates it does not export the
+ *    symbol, which is how a caller detects support. */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -291,6 +295,36 @@ int  mpopis_env_query(mpopis_handle *h, double *reward, int32_t *within, double 
 /* pol.logger.trajectories (src/mppi_mpopi_policies.jl:92-95, src/utils.jl:139-141): B x K x (H x ss),
  * state after each model step of the LAST simulate_model call; needs cfg.log_trajectories. */
 int  mpopis_get_trajectories(mpopis_handle *h, double *out);
+
+/* The plan of the last policy step and its best samples: what the reference's plot(env, pol, perc) draws (src/envs/plots.jl:96-169: the
+ * trajectories in the order sortperm(pol.logger.traj_weights, rev=true)), plus the trajectory of the chosen plan itself, which is no sample.
+ * Needs no cfg.log_trajectories and adds nothing to a policy step: on request the `top` highest-weight samples are picked on the device, their
+ * control sequences and the plan's are rolled out once more (top + 1 rollouts per slot, no control-cost term) and only those come back.
+ *   top        0 .. min(K, MPOPIS_PLAN_MAX_TOP); 0 returns the plan alone.  Anything else: MPOPIS_ERR_ARG.
+ *   controls   B*cs           weighted_controls = U_orig + weighted noise of the last step (:137,:230), UNCLAMPED and before the roll: the same
+ *                             addition the step performed, so controls[as:] equals the rolled pol.U[:cs-as] and clamp(controls[:as]) the returned
+ *                             control, bit for bit
+ *   traj       B x (top+1) x (H x ss col-major, as mpopis_get_trajectories): entry 0 = the states the plan predicts from the state the step
+ *                             started from, entry j = those of sample idx0[j-1]
+ *   cost       B x (top+1)    -sum of the rewards along each of those rollouts; NO control-cost term, whatever γ is
+ *   idx0       B x top        0-based sample indices in descending weight, equal weights with the lower index first: the stable order of
+ *                             sortperm(weights, rev=true)[1:top].  Exact.  (Ties are the normal case: with a small λ most weights underflow to 0.)
+ *   weights    B x top        weights[idx0[j]]
+ * Any output pointer may be NULL.  Entry 0 is rolled out from controls itself; entry j from U_orig + E_out[:, idx0[j-1]], with E_out the noise
+ * "after the final shift" that mpopis_policy_step returns, so a caller can reproduce every rollout from U_orig and E_out.
+ * Source and validity: the call reads the last successful mpopis_policy_step / mpopis_policy_call of the handle, which stays readable only
+ * until another call writes to the handle.  The getters keep it: mpopis_get_state, mpopis_get_U, mpopis_get_Sigma, mpopis_get_slot_hyper,
+ * mpopis_get_trajectories, mpopis_env_query, mpopis_last_error, mpopis_timing_read and mpopis_get_plan itself.  EVERY other entry point ends it
+ * (mpopis_env_step, mpopis_set_state, mpopis_set_U, mpopis_reset, mpopis_rollout_costs, mpopis_run_trials, mpopis_bench_policy_steps, every
+ * setter, the timing switches, the communicator calls), and so does a step that returned an error.  Without a valid source the call returns
+ * MPOPIS_ERR_ARG and mpopis_last_error says which of the three applies: no step yet, the last step failed, or which call wrote.
+ * The call is synchronous and changes nothing a later step reads: pol.U, the RNG position, cost, weights, E, the logger's trajectories and the
+ * iteration counts stay as they are, and a handle that calls it computes the same bits afterwards as one that never does.  Its device buffers
+ * (B (top+1) (cs + H ss + 1) doubles and a little more) are allocated at the first call and grown when a later call asks for a larger top;
+ * MPOPIS_ERR_HIP when that fails, the handle stays usable. */
+#define MPOPIS_PLAN_MAX_TOP 64
+int  mpopis_get_plan(mpopis_handle *h, int32_t top, double *controls /* B*cs */, double *traj /* B*(top+1)*H*ss */,
+                     double *cost /* B*(top+1) */, int32_t *idx0 /* B*top */, double *weights /* B*top */);
 
 /* ---- Level 3: the closed-loop trial harness, device resident ------------------------------------
  * simulate_car_racing / simulate_mountaincar trial loop (src/examples/car_example.jl:170-326,

@@ -5,7 +5,7 @@ reference's operator interface.  There is no CPU fallback: without libmpopis_hip
 MI355X every compute call raises.
 """
 from ._lib import MPOPISError  # noqa: F401
-from .engine import Engine, default_track  # noqa: F401
+from .engine import Engine, default_track, plan_order  # noqa: F401
 from .envs import (CarRacingEnv, CarRacingEnvParams, MultiCarRacingEnv, MountainCarEnv, CartPoleEnv, CustomEnv, Track, state, reward,  # noqa: F401
                    action_space, is_terminated, within_track, calculate_β, exceed_β, pointmass_source, mapnav_source)
 from .policies import (MPPI_Policy, GMPPI_Policy, IMPPI_Policy, CEMPPI_Policy, CMAMPPI_Policy, μAISMPPI_Policy,  # noqa: F401

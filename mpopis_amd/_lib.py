@@ -20,6 +20,7 @@ POLICY_IDS = {"mppi": 0, "gmppi": 1, "imppi": 2, "cemppi": 3, "cmamppi": 4,
 SIGMA_EST_IDS = {"mle": 0, "ss": 1, "lw": 2, "rblw": 3, "oas": 4}
 ERR_ARG, ERR_NOT_PD, ERR_ACTION, ERR_HIP, ERR_NUMERIC = -1, -2, -3, -4, -5
 RECORD_LEN = 16
+PLAN_MAX_TOP = 64          # MPOPIS_PLAN_MAX_TOP
 
 # every symbol include/mpopis.h declares (checked by tests/test_abi.py without a GPU)
 ABI_SYMBOLS = [
@@ -31,6 +32,7 @@ ABI_SYMBOLS = [
     "mpopis_timing_reset", "mpopis_bench_policy_steps",
     "mpopis_create_custom", "mpopis_set_env_table", "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
     "mpopis_set_slot_hyper", "mpopis_get_slot_hyper", "mpopis_set_Sigma_slots", "mpopis_set_env_params_slots", "mpopis_set_tracks",
+    "mpopis_get_plan",
 ]
 
 
@@ -81,6 +83,8 @@ def lib():
         if hasattr(L, "mpopis_set_env_params_slots"):           # (per-slot env parameters and tracks: newer still)
             L.mpopis_set_env_params_slots.argtypes = [H, _dp, C.c_int32]
             L.mpopis_set_tracks.argtypes = [H, C.c_int32, _ip, _dp, _dp, _dp, _ip]
+        if hasattr(L, "mpopis_get_plan"):                       # (the plan read-out: newest)
+            L.mpopis_get_plan.argtypes = [H, C.c_int32, _dp, _dp, _dp, _ip, _dp]
         L.mpopis_destroy.argtypes = [H]
         L.mpopis_destroy.restype = None
         L.mpopis_set_env_params.argtypes = [H, _dp, C.c_int32]

@@ -319,6 +319,12 @@ AliasForm alias_build_form(int K, bool have_need_ws, bool par_enabled);
 void launch_alias_sample(const double* accept, const int32_t* alias, const int32_t* di, size_t di_stride, const double* du,
                          int32_t* out, int32_t* log, size_t log_stride, int B, int K, const int* active, hipStream_t s);
 
+// kernels_plan.hip (mpopis_get_plan): the top samples of a weight row in the order "weight descending, index ascending" (top <= min(K, MPOPIS_PLAN_MAX_TOP);
+// idx / wsel [B][top]), then controls [B][cs] = Uin + wn and the noise block Eplan [B][cs][top + 1]: column 0 = wn, column j = E[:, idx[j-1]] + (Ucur - Uin)
+void launch_plan_select(const double* w, int B, int K, int top, int32_t* idx, double* wsel, hipStream_t s);
+void launch_plan_assemble(const double* E, const double* Ucur, const double* Uin, const double* wn, const int32_t* idx, int B, int cs, int K, int top,
+                          double* controls, double* Eplan, hipStream_t s);
+
 // kernels_cma.hip
 // kernels_invsqrt.hip: y = A^-1/2 b (Lanczos + quadrature) and fro = tr(A^-1) = scale * ||L^-1||_F^2 with L = chol(scale * A)
 constexpr size_t kInvsqrtPadDoubles = 512;

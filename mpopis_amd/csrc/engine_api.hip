@@ -438,6 +438,7 @@ void mpopis_destroy(mpopis_handle* h) {
     for (auto st : h->xstream) if (st) (void)hipStreamSynchronize(st);
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->custom.d_table) (void)hipFree(h->custom.d_table);
+    if (h->plan.base) (void)hipFree(h->plan.base);
     if (h->custom.module) (void)hipModuleUnload(h->custom.module);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
     if (h->h_call) (void)hipHostFree(h->h_call);
@@ -453,6 +454,7 @@ void mpopis_destroy(mpopis_handle* h) {
 }
 
 int mpopis_set_env_params(mpopis_handle* h, const double* p, int32_t n) {
+    if (h) h->plan_drop("mpopis_set_env_params");
     if (!h || !p) return MPOPIS_ERR_ARG;
     if (h->env.kind == MPOPIS_ENV_CUSTOM) {
         if (n != h->custom.nparams) { h->err = "custom env expects " + std::to_string(h->custom.nparams) + " parameters"; return MPOPIS_ERR_ARG; }
@@ -499,6 +501,7 @@ int mpopis_handle::sync_slot_env() {
 // One parameter vector per slot.  A setup call: the [B] struct array is written only after everything queued has finished (the rollout kernels read
 // it through the constant address space).  Everything is checked and formed on the host first, so a refused call changes nothing.
 int mpopis_set_env_params_slots(mpopis_handle* h, const double* p, int32_t n) {
+    if (h) h->plan_drop("mpopis_set_env_params_slots");
     if (!h) return MPOPIS_ERR_ARG;
     if (!p) { h->err = "mpopis_set_env_params_slots: p is NULL"; return MPOPIS_ERR_ARG; }
     const int kind = h->env.kind, B = h->B_full;
@@ -535,6 +538,7 @@ int mpopis_set_env_params_slots(mpopis_handle* h, const double* p, int32_t n) {
 // too, before the buffer is written or replaced -- the global-memory rollout kernel reads the table through the constant address space, which
 // holds only while nothing writes it under a running kernel.
 int mpopis_set_env_table(mpopis_handle* h, const double* data, int64_t n, int32_t per_slot) {
+    if (h) h->plan_drop("mpopis_set_env_table");
     if (!h) return MPOPIS_ERR_ARG;
     if (h->env.kind != MPOPIS_ENV_CUSTOM) { h->err = "mpopis_set_env_table: not a custom handle (only an env built with MPOPIS_DEFINE_ENV_TABLE of mpopis_env.h takes a table)"; return MPOPIS_ERR_ARG; }
     if (!h->custom.has_table) { h->err = "mpopis_set_env_table: the handle's code object has no mpopis_env_table_abi (build the env with MPOPIS_DEFINE_ENV_TABLE)"; return MPOPIS_ERR_ARG; }
@@ -586,6 +590,7 @@ static int upload_track(mpopis_handle* h, const double* x, const double* y, cons
 }
 
 int mpopis_set_track(mpopis_handle* h, const double* x, const double* y, const double* w, int32_t P) {
+    if (h) h->plan_drop("mpopis_set_track");
     if (!h || !x || !y || !w || P < 2 || P > mpopis::kMaxTrackPoints) { if (h) h->err = "bad track (need 2 <= P <= 2048 points)"; return MPOPIS_ERR_ARG; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Track tk;
@@ -604,6 +609,7 @@ int mpopis_set_track(mpopis_handle* h, const double* x, const double* y, const d
 // into fresh buffers that the handle keeps until mpopis_destroy (a launch still queued may read the old ones): ~170 B per track point per call.  A setup call like mpopis_set_env_params_slots;
 // the handle changes only once every track is on the device.
 int mpopis_set_tracks(mpopis_handle* h, int32_t ntracks, const int32_t* P, const double* x, const double* y, const double* w, const int32_t* track_of_slot) {
+    if (h) h->plan_drop("mpopis_set_tracks");
     if (!h) return MPOPIS_ERR_ARG;
     const int B = h->B_full;
     if (h->env.kind != MPOPIS_ENV_CAR) { h->err = "mpopis_set_tracks: not a car handle (only the car env drives on a track)"; return MPOPIS_ERR_ARG; }
@@ -638,12 +644,14 @@ int mpopis_set_tracks(mpopis_handle* h, int32_t ntracks, const int32_t* P, const
 }
 
 int mpopis_set_action_bounds(mpopis_handle* h, const double* lo, const double* hi) {
+    if (h) h->plan_drop("mpopis_set_action_bounds");
     if (!h || !lo || !hi) return MPOPIS_ERR_ARG;
     for (int i = 0; i < h->as; ++i) { h->env.lo[i] = lo[i]; h->env.hi[i] = hi[i]; }
     return MPOPIS_OK;
 }
 
 int mpopis_reset(mpopis_handle* h) {
+    if (h) h->plan_drop("mpopis_reset");
     if (!h) return MPOPIS_ERR_ARG;
     std::vector<double> x((size_t)h->B * h->ss, 0.0);
     for (int b = 0; b < h->B; ++b) {
@@ -661,10 +669,13 @@ int mpopis_reset(mpopis_handle* h) {
         // CartPole: reference draws 0.1*rand(4) - 0.05; deterministic centre = all zeros
     }
     std::vector<int> z(h->B, 0);
-    return mpopis_set_state(h, x.data(), z.data(), z.data());
+    const int rc = mpopis_set_state(h, x.data(), z.data(), z.data());
+    h->plan_drop("mpopis_reset");
+    return rc;
 }
 
 int mpopis_set_state(mpopis_handle* h, const double* x, const int32_t* t, const int32_t* done) {
+    if (h) h->plan_drop("mpopis_set_state");
     if (!h || !x) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpyAsync(h->d_x, x, sizeof(double) * h->B * h->ss, hipMemcpyHostToDevice, h->stream));
@@ -685,6 +696,7 @@ int mpopis_get_state(mpopis_handle* h, double* x, int32_t* t, int32_t* done) {
 }
 
 int mpopis_set_U(mpopis_handle* h, const double* U) {
+    if (h) h->plan_drop("mpopis_set_U");
     if (!h || !U) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpyAsync(h->d_U, U, sizeof(double) * h->B * h->cs, hipMemcpyHostToDevice, h->stream));
@@ -791,16 +803,19 @@ static int set_Sigma0(mpopis_handle* h, const double* Sigma, int32_t n, bool per
 // for :mppi the as x as Σ is kept by the reference, which is the same distribution as the
 // block-diagonal cs x cs one used here (Cholesky of a block-diagonal matrix is block-diagonal).
 int mpopis_set_Sigma(mpopis_handle* h, const double* Sigma, int32_t n) {
+    if (h) h->plan_drop("mpopis_set_Sigma");
     if (!h || !Sigma) return MPOPIS_ERR_ARG;
     return set_Sigma0(h, Sigma, n, false);
 }
 int mpopis_set_Sigma_slots(mpopis_handle* h, const double* Sigma, int32_t n) {
+    if (h) h->plan_drop("mpopis_set_Sigma_slots");
     if (!h || !Sigma) { if (h) h->err = "mpopis_set_Sigma_slots: null argument"; return MPOPIS_ERR_ARG; }
     return set_Sigma0(h, Sigma, n, true);
 }
 
 // λ, α, λ_ais, σ per slot.  A setup call (it waits for everything queued); the kernels read what is formed here on the host.
 int mpopis_set_slot_hyper(mpopis_handle* h, const double* lambda, const double* alpha, const double* lambda_ais, const double* cma_sigma) {
+    if (h) h->plan_drop("mpopis_set_slot_hyper");
     if (!h) return MPOPIS_ERR_ARG;
     const int B = h->B_full, K = h->K;
     if (h->cfg.policy == MPOPIS_POL_NESMPPI && cma_sigma)
@@ -855,6 +870,7 @@ int mpopis_get_slot_hyper(mpopis_handle* h, double* lambda, double* alpha, doubl
 }
 
 int mpopis_seed(mpopis_handle* h, uint64_t seed) {
+    if (h) h->plan_drop("mpopis_seed");
     if (!h) return MPOPIS_ERR_ARG;
     std::vector<uint64_t> s(h->B);
     for (int b = 0; b < h->B; ++b) s[b] = seed + (uint64_t)b + 1;              // seed!(pol, seed + k), car_example.jl:188
@@ -866,6 +882,7 @@ int mpopis_seed(mpopis_handle* h, uint64_t seed) {
 }
 
 int mpopis_seed_slots(mpopis_handle* h, const uint64_t* seeds) {
+    if (h) h->plan_drop("mpopis_seed_slots");
     if (!h || !seeds) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, sizeof(uint64_t) * h->B, hipMemcpyHostToDevice, h->stream));
@@ -892,6 +909,7 @@ int mpopis_get_Sigma(mpopis_handle* h, double* out) {
 
 int mpopis_rollout_costs(mpopis_handle* h, const double* x0, const double* U, const double* U_orig, const double* E,
                          const double* Sigma_inv, double* cost) {
+    if (h) h->plan_drop("mpopis_rollout_costs");
     if (!h || !U || !E || !cost) return MPOPIS_ERR_ARG;
     if (h->track_missing()) return MPOPIS_ERR_ARG;
     if (h->use_gvec() && !Sigma_inv) { h->err = "Sigma_inv required when alpha != 1"; return MPOPIS_ERR_ARG; }
@@ -919,6 +937,7 @@ int mpopis_rollout_costs(mpopis_handle* h, const double* x0, const double* U, co
 }
 
 int mpopis_env_step(mpopis_handle* h, const double* action, double* reward) {
+    if (h) h->plan_drop("mpopis_env_step");
     if (!h || !action) return MPOPIS_ERR_ARG;
     if (h->track_missing()) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -953,8 +972,80 @@ int mpopis_get_trajectories(mpopis_handle* h, double* out) {
     return MPOPIS_OK;
 }
 
+// The plan's buffers for every top up to the one asked for, carved out of one allocation (each part 16-byte aligned).  A larger request replaces
+// the block; the handle is idle then (the call that used the old one ended with a stream wait).  On failure the old block stays.
+int mpopis_handle::plan_reserve(int top) {
+    if (top <= plan.cap_top) return MPOPIS_OK;
+    const size_t W = (size_t)top + 1, Bn = (size_t)B_full;
+    auto up = [](size_t n) { return (n + 1) & ~(size_t)1; };     // doubles, rounded up to 16 bytes
+    const size_t n_controls = up(Bn * cs), n_E = up(Bn * cs * W), n_traj = up(Bn * W * ss * T), n_cost = up(Bn * W), n_w = up(Bn * std::max(top, 1));
+    const size_t n_idx = up((Bn * std::max(top, 1) + 1) / 2);       // int32 pairs
+    const size_t bytes = sizeof(double) * (n_controls + n_E + n_traj + n_cost + n_w + n_idx);
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        err = "mpopis_get_plan: hipMalloc of the plan buffers failed (" + std::to_string(bytes) + " bytes)";
+        return MPOPIS_ERR_HIP;
+    }
+    if (plan.base) (void)hipFree(plan.base);
+    plan.base = p; plan.cap_top = top;
+    double* d = (double*)p;
+    plan.controls = d; d += n_controls;
+    plan.E = d; d += n_E;
+    plan.traj = d; d += n_traj;
+    plan.cost = d; d += n_cost;
+    plan.w = d; d += n_w;
+    plan.idx = (int32_t*)d;
+    HIPCHK(this, hipMemsetAsync(p, 0, bytes, stream));
+    return MPOPIS_OK;
+}
+
+// The plan of the last policy step and its `top` highest-weight sample rollouts (include/mpopis.h).  A getter: everything it reads -- d_w, d_E,
+// d_Ucur, d_Uin, d_wn and the step's start state d_x / d_xext -- is still resident, and it writes the plan's own buffers only.
+int mpopis_get_plan(mpopis_handle* h, int32_t top, double* controls, double* traj, double* cost, int32_t* idx0, double* weights) {
+    if (!h) return MPOPIS_ERR_ARG;
+    if (!h->plan_ok) {
+        const std::string by = h->plan_lost;
+        if (!h->plan_stepped) h->err = "mpopis_get_plan: no mpopis_policy_step or mpopis_policy_call has run on this handle yet";
+        else if (by == "mpopis_policy_step" || by == "mpopis_policy_call") h->err = "mpopis_get_plan: the last policy step returned an error; there is no plan to read";
+        else h->err = "mpopis_get_plan: " + by + " has written to the handle since the last policy step; the plan is read before any other call that is no getter";
+        return MPOPIS_ERR_ARG;
+    }
+    const int B = h->B, K = h->K, cs = h->cs;
+    if (top < 0 || top > std::min(K, MPOPIS_PLAN_MAX_TOP)) {
+        h->err = "mpopis_get_plan: top must be 0.." + std::to_string(std::min(K, MPOPIS_PLAN_MAX_TOP)) + " (min(K, MPOPIS_PLAN_MAX_TOP)), got " + std::to_string(top);
+        return MPOPIS_ERR_ARG;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (const int rc = h->plan_reserve(top)) return rc;
+    const size_t W = (size_t)top + 1;
+    mpopis_handle::PlanBufs& pl = h->plan;
+    launch_plan_select(h->d_w, B, K, top, pl.idx, pl.w, h->stream);
+    launch_plan_assemble(h->d_E, h->d_Ucur, h->d_Uin, h->d_wn, pl.idx, B, cs, K, top, pl.controls, pl.E, h->stream);
+    if (traj || cost) {
+        // the extended start states once more, from the d_x the step started from: a step that ran as part-chains left each part's in that part's
+        // own view of d_xext (its slot stride is that of kMaxCars cars), not in the whole batch's
+        h->prepare_state();
+        hipError_t custom_err = hipSuccess;
+        if (!h->plan_rollout((int)W, &custom_err)) {
+            h->err = h->env.kind == MPOPIS_ENV_CUSTOM ? std::string("mpopis_get_plan: launching the custom env's rollout kernel failed: ") + hipGetErrorString(custom_err)
+                                                      : std::string("mpopis_get_plan: no rollout kernel for this env");
+            return MPOPIS_ERR_HIP;
+        }
+    }
+    if (controls) HIPCHK(h, hipMemcpyAsync(controls, pl.controls, sizeof(double) * B * cs, hipMemcpyDeviceToHost, h->stream));
+    if (traj) HIPCHK(h, hipMemcpyAsync(traj, pl.traj, sizeof(double) * B * W * h->ss * h->T, hipMemcpyDeviceToHost, h->stream));
+    if (cost) HIPCHK(h, hipMemcpyAsync(cost, pl.cost, sizeof(double) * B * W, hipMemcpyDeviceToHost, h->stream));
+    if (top > 0 && idx0) HIPCHK(h, hipMemcpyAsync(idx0, pl.idx, sizeof(int32_t) * B * top, hipMemcpyDeviceToHost, h->stream));
+    if (top > 0 && weights) HIPCHK(h, hipMemcpyAsync(weights, pl.w, sizeof(double) * B * top, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, wait_stream(h->stream));
+    HIPCHK(h, hipGetLastError());
+    return MPOPIS_OK;
+}
+
 int mpopis_policy_step(mpopis_handle* h, const mpopis_noise* noise, double* control, double* cost, double* weights,
                        double* E_out, int32_t* resample_idx0, int32_t* iters_run) {
+    if (h) h->plan_step_begins("mpopis_policy_step");
     if (!h) return MPOPIS_ERR_ARG;
     if (h->track_missing()) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -993,6 +1084,7 @@ int mpopis_policy_step(mpopis_handle* h, const mpopis_noise* noise, double* cont
         if (iters_run) memcpy(iters_run, h->h_pin + (size_t)B * h->as, sizeof(int) * B);
     }
     HIPCHK(h, hipGetLastError());
+    h->plan_ok = rc == MPOPIS_OK;                               // what mpopis_get_plan reads stays resident until the next writing call
     return rc;
 }
 
@@ -1001,6 +1093,7 @@ int mpopis_policy_step(mpopis_handle* h, const mpopis_noise* noise, double* cont
 // outputs travel through the handle's device-mapped mailbox, so the stream carries kernels only.
 int mpopis_policy_call(mpopis_handle* h, const double* x, const int32_t* t, const int32_t* done, double* U_inout, const mpopis_noise* noise,
                        double* control, double* cost, double* weights, int32_t* iters_run) {
+    if (h) h->plan_step_begins("mpopis_policy_call");
     if (!h) return MPOPIS_ERR_ARG;
     if (!h->h_call || (noise && noise->Z)) {
         // injected noise is a parity-test path (megabytes of host data): plain composition of the four calls
@@ -1063,10 +1156,12 @@ int mpopis_policy_call(mpopis_handle* h, const double* x, const int32_t* t, cons
     if (iters_run) memcpy(iters_run, hb.iters, sizeof(int) * B);
     rc = fold_status(h, hb.status);
     HIPCHK(h, hipGetLastError());
+    h->plan_ok = rc == MPOPIS_OK;
     return rc;
 }
 
 int mpopis_set_state_noise(mpopis_handle* h, double sigma_x, double sigma_y, double sigma_psi) {
+    if (h) h->plan_drop("mpopis_set_state_noise");
     if (!h) return MPOPIS_ERR_ARG;
     if (!(sigma_x >= 0.0 && sigma_y >= 0.0 && sigma_psi >= 0.0)) { h->err = "state noise sigmas must be >= 0"; return MPOPIS_ERR_ARG; }
     h->noise_sx = sigma_x; h->noise_sy = sigma_y; h->noise_spsi = sigma_psi;
@@ -1074,11 +1169,13 @@ int mpopis_set_state_noise(mpopis_handle* h, double sigma_x, double sigma_y, dou
 }
 
 int mpopis_run_trials(mpopis_handle* h, int32_t num_steps, int32_t laps, double* records, double* actions) {
+    if (h) h->plan_drop("mpopis_run_trials");
     if (!h || !records) return MPOPIS_ERR_ARG;
     return h->run_trials(num_steps, laps, records, actions);
 }
 
 int mpopis_set_overlap(mpopis_handle* h, int32_t on) {
+    if (h) h->plan_drop("mpopis_set_overlap");
     if (!h) return MPOPIS_ERR_ARG;
     if (h->split_pinned) return MPOPIS_OK;
     if (on <= 0) { h->nsplit = 1; h->split_auto = true; return MPOPIS_OK; }                   // the default: the engine picks (auto_parts)
@@ -1088,6 +1185,7 @@ int mpopis_set_overlap(mpopis_handle* h, int32_t on) {
 }
 
 int mpopis_timing_enable(mpopis_handle* h, int32_t on) {
+    if (h) h->plan_drop("mpopis_timing_enable");
     if (!h) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (on && h->events.empty()) {
@@ -1100,7 +1198,7 @@ int mpopis_timing_enable(mpopis_handle* h, int32_t on) {
     h->timing_mask = (on == 1 || on == 0) ? ~0 : (on >> 1);     // 1: every class; otherwise bit (class + 1) selects a class
     return MPOPIS_OK;
 }
-int mpopis_timing_reset(mpopis_handle* h) { if (!h) return MPOPIS_ERR_ARG; h->ev_used = 0; h->ev_slot.clear(); return MPOPIS_OK; }
+int mpopis_timing_reset(mpopis_handle* h) { if (h) h->plan_drop("mpopis_timing_reset"); if (!h) return MPOPIS_ERR_ARG; h->ev_used = 0; h->ev_slot.clear(); return MPOPIS_OK; }
 int mpopis_timing_read(mpopis_handle* h, char* names, int32_t names_cap, double* ms_total, int64_t* launches, int32_t* n) {
     if (!h || !n) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1121,6 +1219,7 @@ int mpopis_timing_read(mpopis_handle* h, char* names, int32_t names_cap, double*
 }
 
 int mpopis_bench_policy_steps(mpopis_handle* h, int32_t steps, double* ms, double* rollouts) {
+    if (h) h->plan_drop("mpopis_bench_policy_steps");
     if (!h || steps < 0) return MPOPIS_ERR_ARG;
     if (h->track_missing()) return MPOPIS_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1164,14 +1263,31 @@ void mpopis_handle::prepare_state() {
     if (env.kind == MPOPIS_ENV_CAR) launch_extend_state(d_x, d_xext, B, env.ncars, stream, env.track, slot_tracks());
 }
 
-void mpopis_handle::rollout(const double* Ucur, const double* Uorig, const double* gvec, const int* act, int* iters, int iter_n) {
+RolloutArgs mpopis_handle::rollout_base() const {
     RolloutArgs a;
-    a.env = env; a.B = B; a.K = K; a.T = T; a.cs = cs;
-    a.x0 = d_x; a.x0ext = d_xext; a.t0 = d_t; a.done0 = d_done; a.Ucur = Ucur; a.Uorig = Uorig; a.E = d_E; a.gvec = gvec;
+    a.env = env; a.B = B; a.K = 0; a.T = T; a.cs = cs;
+    a.x0 = d_x; a.x0ext = d_xext; a.t0 = d_t; a.done0 = d_done;
+    a.Ucur = a.Uorig = a.E = a.gvec = nullptr; a.cost = a.traj = nullptr;
+    a.active = nullptr; a.iters = nullptr; a.iter_n = 0; a.cmin = nullptr; a.status = nullptr;
+    a.senv = slot_env();
+    return a;
+}
+
+// The read-out's rollout: nominal controls U_orig, noise block plan.E, no control cost, every slot, nothing of the step's own outputs touched.
+// Not a launch of a policy step: outside the timing classes.
+bool mpopis_handle::plan_rollout(int Kp, hipError_t* custom_err) {
+    RolloutArgs a = rollout_base();
+    a.K = Kp; a.Ucur = d_Uin; a.Uorig = d_Uin; a.E = plan.E;
+    a.cost = plan.cost; a.traj = plan.traj;
+    return launch_rollout(a, stream, custom_err);
+}
+
+void mpopis_handle::rollout(const double* Ucur, const double* Uorig, const double* gvec, const int* act, int* iters, int iter_n) {
+    RolloutArgs a = rollout_base();
+    a.K = K; a.Ucur = Ucur; a.Uorig = Uorig; a.E = d_E; a.gvec = gvec;
     a.cost = d_cost; a.traj = d_traj; a.active = act; a.iters = iters; a.iter_n = iter_n;
     a.cmin = weights_in_moments ? d_cmin : nullptr; a.status = weights_in_moments ? d_status : nullptr;
     a.share = coop_share;
-    a.senv = slot_env();
     time_begin(0);
     hipError_t custom_err = hipSuccess;
     if (!launch_rollout(a, stream, &custom_err) && launch_err.empty())

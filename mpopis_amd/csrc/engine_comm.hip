@@ -77,6 +77,7 @@ int mpopis_comm_unique_id(char* id128) {
 }
 
 int mpopis_comm_init(mpopis_handle* h, const char* id128, int32_t rank, int32_t world) {
+    if (h) h->plan_drop("mpopis_comm_init");
     if (!h || world < 1 || rank < 0 || rank >= world) { if (h) h->err = "mpopis_comm_init: need 0 <= rank < world"; return MPOPIS_ERR_ARG; }
     if (h->comm) { h->err = "communicator already initialised"; return MPOPIS_ERR_ARG; }
     h->comm_rank = rank; h->comm_world = world;
@@ -97,6 +98,7 @@ int mpopis_comm_init(mpopis_handle* h, const char* id128, int32_t rank, int32_t 
 // (world == 1 without an id, or mpopis_comm_init never ran / failed).  A launcher uses it to tell "the gather went over RCCL with N ranks"
 // from "it silently ran some other way".
 int mpopis_comm_count(mpopis_handle* h, int32_t* ranks) {
+    if (h) h->plan_drop("mpopis_comm_count");
     if (!h || !ranks) { if (h) h->err = "mpopis_comm_count: null argument"; return MPOPIS_ERR_ARG; }
     *ranks = 0;
     if (!h->comm) return MPOPIS_OK;
@@ -109,6 +111,7 @@ int mpopis_comm_count(mpopis_handle* h, int32_t* ranks) {
 }
 
 int mpopis_comm_destroy(mpopis_handle* h) {
+    if (h) h->plan_drop("mpopis_comm_destroy");
     if (!h) return MPOPIS_ERR_ARG;
     if (h->comm) {
         (void)hipSetDevice(h->cfg.device);
@@ -125,6 +128,7 @@ int mpopis_comm_destroy(mpopis_handle* h) {
 // counts[world].  ncclGather when the library has it (RCCL extension), otherwise ncclAllGather (same bytes per link:
 // the payload is < 1 kB per rank).
 int mpopis_gather_summary(mpopis_handle* h, const double* records, int32_t n_local, int32_t n_max, double* out, int32_t* counts) {
+    if (h) h->plan_drop("mpopis_gather_summary");
     if (!h || n_local < 0 || n_max < n_local || (n_local > 0 && !records)) { if (h) h->err = "mpopis_gather_summary: bad arguments"; return MPOPIS_ERR_ARG; }
     const int world = h->comm_world, rank = h->comm_rank;
     const size_t RL = MPOPIS_RECORD_LEN, per = 1 + (size_t)n_max * RL;

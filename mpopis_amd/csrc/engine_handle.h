@@ -157,9 +157,25 @@ struct mpopis_handle {
     bool debug_launch = false; int cur_class = 0; std::string launch_err;
     std::vector<hipEvent_t> events; std::vector<int> ev_slot; int ev_used = 0;
 
+    // mpopis_get_plan: the read-out of the last policy step (kernels_plan.hip).  plan_ok: that step succeeded and no entry point has written to the
+    // handle since -- set at the end of a successful mpopis_policy_step / mpopis_policy_call, cleared by plan_drop at the top of every entry point
+    // that is no getter (plan_lost: its name, plan_stepped: a policy step has been asked for at all -- for the refusal's message).  The buffers are
+    // ONE allocation of the whole batch, made at the first call and replaced when a call asks for a larger top; no slot views (the call runs on
+    // the unsplit batch only).
+    bool plan_ok = false, plan_stepped = false; const char* plan_lost = "";
+    void plan_drop(const char* by) { plan_ok = false; plan_lost = by; }
+    void plan_step_begins(const char* by) { plan_drop(by); plan_stepped = true; }
+    struct PlanBufs {
+        void* base = nullptr; int cap_top = -1;
+        double *controls = nullptr, *E = nullptr, *traj = nullptr, *cost = nullptr, *w = nullptr; int32_t* idx = nullptr;
+    } plan;
+    int plan_reserve(int top);                                 // engine_api.hip; sets err
+    bool plan_rollout(int Kp, hipError_t* custom_err);         // the plan's Kp = top + 1 control sequences from the step's start state into plan.traj / plan.cost
+
     void time_begin(int slot);
     void time_end();
     void prepare_state();
+    mpopis::RolloutArgs rollout_base() const;                  // what every rollout of the handle shares: env, shape, start state, per-slot env
     void rollout(const double* Ucur, const double* Uorig, const double* gvec, const int* act, int* iters = nullptr, int iter_n = 0);
     int B_full = 0;                                       // cfg.batch (B is narrowed to a part's slots while a part-chain is enqueued)
     // What the scatter kernel's form goes by (launch_wcov_mfma): the whole batch -- or -1 = "the compact form" for shapes whose DEFAULT schedule is

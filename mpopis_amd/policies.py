@@ -100,6 +100,13 @@ class AbstractPathIntegralPolicy:
             return control, {k: v[0] for k, v in out.items()}
         return control
 
+    def plan(self, top=0):
+        """The plan pol(env) just chose and its `top` highest-weight samples: slot 0 of Engine.get_plan -- dict(controls (cs,), traj (top+1, T, ss),
+        cost (top+1,), idx0 (top,), weights (top,)).  traj[1:] in the order idx0 is what the reference's plot(env, pol, perc) thins and draws
+        (src/envs/plots.jl:96-126), without log=True; traj[0] is the predicted trajectory of the chosen controls.  Valid until the policy is
+        called, seeded or given a new U."""
+        return {k: v[0] for k, v in self._eng.get_plan(top).items()}
+
     def close(self):
         self._eng.close()
 
