@@ -216,7 +216,9 @@ __device__ __forceinline__ void wcov_rows_chunk(const double* __restrict__ xl, v
 // rows from the same registers per thread (25 per chunk of 16 columns: 800 rows), and the 8 waves take 56 tile pairs; one workgroup per CU
 // (800 x 17 x 8 B = 106 KB of LDS), i.e. the same two waves per SIMD as the 4-wave form at two workgroups per CU.
 constexpr int kWcovTallRows = 800;
-template <int KC, bool SQ, bool ROWS = false, bool TALL = false>
+// NT (pair list with 64-column chunks: cs <= 112, four waves): the number of row tiles as a compile-time constant, which makes the staging
+// straight-line (stage_chunk); 0 = known at run time only, the guarded staging.
+template <int KC, bool SQ, bool ROWS = false, bool TALL = false, int NT = 0>
 __global__ void __launch_bounds__(ROWS || TALL ? 512 : 256, ROWS || TALL ? 1 : 2) k_wcov_mfma_partial(const double* __restrict__ X, const double* __restrict__ w, const int32_t* __restrict__ idx,
                                                            const double* __restrict__ mu, const double* __restrict__ rscale,
                                                            double* __restrict__ part, int cs, int K, int m,
@@ -230,6 +232,7 @@ __global__ void __launch_bounds__(ROWS || TALL ? 512 : 256, ROWS || TALL ? 1 : 2
     const int nt = (cs + 15) / 16, rows_pad = nt * 16;
     static_assert(!ROWS || (KC == 64 && !SQ), "row form: 64-column chunks, plain scatter");
     static_assert(!TALL || (KC == 16 && !ROWS), "tall form: 16-column chunks, pair list");
+    static_assert(NT == 0 || (KC == 64 && !ROWS && NT <= 7), "constant tile count: the 4-wave pair list with 64-column chunks");
     constexpr int S = ROWS ? kRowsS : KC + 1;                   // LDS row stride (doubles); pair-list form: odd strides measured best (tools/kbench)
     constexpr int NTHR = ROWS || TALL ? 512 : 256;
     constexpr int kRowStep = NTHR / KC;
@@ -289,7 +292,8 @@ __global__ void __launch_bounds__(ROWS || TALL ? 512 : 256, ROWS || TALL ? 1 : 2
         const int col = ib ? ib[kq] : kq;
         wreg = costp ? wsl[kq - kbeg] : (wb ? sqrt(wb[col]) : 1.0);      // sqrt(w_k)
 #pragma unroll
-        for (int u = 0; u < kMaxLd; ++u) xreg[u] = Xb[(size_t)min(sr0 + u * kRowStep, cs - 1) * K + col];
+        for (int u = 0; u < kMaxLd; ++u)
+            if (NT == 0 || u * kRowStep < NT * 16) xreg[u] = Xb[(size_t)min(sr0 + u * kRowStep, cs - 1) * K + col];      // (rows beyond the padding are never staged)
     };
     // per-pair operand bases in the MFMA lane pattern (row = tile*16 + li, column offset lk)
     const double* pA[kPairsPerWave]; const double* pB[kPairsPerWave];
@@ -310,6 +314,28 @@ __global__ void __launch_bounds__(ROWS || TALL ? 512 : 256, ROWS || TALL ? 1 : 2
                 const int row = sr0 + u * kRowStep;
                 double v = weighted ? xreg[u] * swk : (kin_cur ? xreg[u] : 0.0);
                 if (u * kRowStep + kRowStep > 96) v = (row < cs) ? v : ((aug && row == cs) ? swk : 0.0);
+                d0[(size_t)u * kRowStep * S] = v;
+            }
+            return;
+        }
+        if constexpr (NT > 0) {
+            // straight-line form of the pair list: with the tile count a constant, every element whose row step ends at or below the last row tile,
+            // u kRowStep + kRowStep <= 16 (NT - 1), is a data row whatever sr0 < kRowStep and cs in 16 (NT - 1) + 1 .. 16 NT are: one multiply and
+            // one ds_write at a fixed offset from d0, no select and no exec region.  Only the last tile's elements look at cs (data row, ones row,
+            // zero padding); rows beyond the padding are not stored.
+            // A column outside [kbeg, kend) is zeroed THROUGH ITS WEIGHT (swk = 0), not by a select: x 0 = +-0 and the accumulators start at +0, so
+            // the partials keep their bits for finite data.  Such a column's address is clamped to column kend - 1, which lies inside the range: a
+            // non-finite value there makes the same entries of the scatter non-finite with or without the NaN = inf 0 of the padding columns.
+            // Unweighted: swk = 1 inside the range, and x 1 = x.
+            const double swk = kin_cur ? sw : 0.0;
+            double* d0 = dst + (size_t)sr0 * S + skk;
+#pragma unroll
+            for (int u = 0; u < kMaxLd; ++u) {
+                if (u * kRowStep >= NT * 16) continue;
+                double v = xreg[u];
+                if (SQ) { v = (v - mureg[u]) * rsreg[u]; v *= v; }
+                v *= swk;
+                if (u * kRowStep + kRowStep > (NT - 1) * 16) { const int row = sr0 + u * kRowStep; v = (row < cs) ? v : ((aug && row == cs) ? swk : 0.0); }
                 d0[(size_t)u * kRowStep * S] = v;
             }
             return;
@@ -610,6 +636,14 @@ WcovForm wcov_form(int cs, int K, int m, int ksplit, int batch, bool has_rscale,
     f.partial = tall ? WCOV_TALL : rows ? WCOV_ROWS : wcov_kc(cs) == 64 ? WCOV_PAIR64 : WCOV_PAIR16;
     return f;
 }
+// the 4-wave pair list with 64-column chunks, instantiated per row-tile count (1..7)
+template <bool SQ, int NT = 7, class... Args>
+static void launch_wcov_pair64(int nt, dim3 grid, size_t lds, hipStream_t s, Args... args) {
+    if constexpr (NT > 1) { if (nt != NT) { launch_wcov_pair64<SQ, NT - 1>(nt, grid, lds, s, args...); return; } }
+    static std::atomic<unsigned long long> seen;
+    ensure_dyn_lds((const void*)k_wcov_mfma_partial<64, SQ, false, false, NT>, 96 * 1024, seen);
+    hipLaunchKernelGGL((k_wcov_mfma_partial<64, SQ, false, false, NT>), grid, dim3(256), lds, s, args...);
+}
 void launch_wcov_mfma(const double* X, const double* w, const int32_t* idx, int m, const double* mu, double* S, double* part,
                       int B, int cs, int K, int ksplit, int sel_batch, double den, double ridge, const int* active, hipStream_t s, const double* rscale,
                       double* mu_out, double* u_add, const double* wsum, const double* cost, unsigned long long* cmin, double neg_inv_lambda,
@@ -623,12 +657,10 @@ void launch_wcov_mfma(const double* X, const double* w, const int32_t* idx, int 
     const int per = ((m + ksplit - 1) / ksplit + kc - 1) / kc * kc;
     const bool rows = form.partial == WCOV_ROWS, tall = form.partial == WCOV_TALL;
     const size_t lds = ((size_t)nt * 16 * (rows ? 2 * kRowsS : kc + 1) + kc + (from_cost ? (rows ? 2 * per : per) : 0)) * sizeof(double);
-    static std::atomic<unsigned long long> seen[5];
-    ensure_dyn_lds((const void*)k_wcov_mfma_partial<64, false, true>, 160 * 1024, seen[4]);
-    ensure_dyn_lds((const void*)k_wcov_mfma_partial<64, false>, 96 * 1024, seen[0]);
-    ensure_dyn_lds((const void*)k_wcov_mfma_partial<16, false>, 96 * 1024, seen[1]);
-    ensure_dyn_lds((const void*)k_wcov_mfma_partial<64, true>, 96 * 1024, seen[2]);
-    ensure_dyn_lds((const void*)k_wcov_mfma_partial<16, true>, 96 * 1024, seen[3]);
+    static std::atomic<unsigned long long> seen[3];
+    ensure_dyn_lds((const void*)k_wcov_mfma_partial<64, false, true>, 160 * 1024, seen[2]);
+    ensure_dyn_lds((const void*)k_wcov_mfma_partial<16, false>, 96 * 1024, seen[0]);
+    ensure_dyn_lds((const void*)k_wcov_mfma_partial<16, true>, 96 * 1024, seen[1]);
     const dim3 grid(ksplit, (npairs + kPairsPerBlock - 1) / kPairsPerBlock, B);
     if (tall) {
         static std::atomic<unsigned long long> seen_t[2];
@@ -641,11 +673,11 @@ void launch_wcov_mfma(const double* X, const double* w, const int32_t* idx, int 
             hipLaunchKernelGGL((k_wcov_mfma_partial<16, false, false, true>), grid_t, dim3(512), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
         }
     } else if (rscale) {
-        if (kc == 64) hipLaunchKernelGGL((k_wcov_mfma_partial<64, true>), grid, dim3(256), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
+        if (kc == 64) launch_wcov_pair64<true>(nt, grid, lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
         else          hipLaunchKernelGGL((k_wcov_mfma_partial<16, true>), grid, dim3(256), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
     } else {
         if (rows)          hipLaunchKernelGGL((k_wcov_mfma_partial<64, false, true>), dim3(ksplit / 2, 1, B), dim3(512), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
-        else if (kc == 64) hipLaunchKernelGGL((k_wcov_mfma_partial<64, false>), grid, dim3(256), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
+        else if (kc == 64) launch_wcov_pair64<false>(nt, grid, lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
         else          hipLaunchKernelGGL((k_wcov_mfma_partial<16, false>), grid, dim3(256), lds, s, X, w, idx, mu, rscale, part, cs, K, m, ksplit, npairs, active, aug, cost, cmin, neg_inv_lambda);
     }
     hipLaunchKernelGGL(k_wcov_mfma_finish, dim3(npairs, B), dim3(256), 0, s, part, w, S, cs, K, ksplit, npairs, den, ridge, active,

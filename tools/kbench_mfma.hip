@@ -18,7 +18,8 @@
 // op 2 TWOKERNEL   like FUSED: launch_potrf, launch_sample_normal, launch_trmm_LZ_mfma                  -> L, Z, E
 // op 3 WCOV        ipar { cs, K, m, ksplit, sel_batch, want_mu_out }    dpar { den, ridge, -1/λ }
 //                  arrays: active, X, w, wsum, idx, mu, rscale, cost, mu_shift, u0 (given: u_add starts there)
-//                  -> S, mu_out, u_add, cmin (u64: the slot minimum in engine.h's cost_key encoding before the launch, whatever the launch left after)
+//                  -> S, mu_out, u_add, cmin (u64: the slot minimum in engine.h's cost_key encoding before the launch, whatever the launch left after),
+//                     part (the K-split partial workspace as the partial kernel left it, no guard: NaN wherever nothing was written)
 //                  form = partial | sq << 8 | aug << 9 | from_cost << 10      (wcov_form)
 // op 4 SHRINK      ipar { cs, m, kind (0 rblw, 1 oas, 2 ss, 3 lw) }  dpar { ridge }   arrays: active, S, Q      -> S, rs
 // op 5 CE_SMALL    ipar { cs, K, m, est, ksplit }  dpar { ridge }    arrays: active, E, order, U                -> mu, S, U
@@ -146,7 +147,8 @@ int main(int argc, char** argv) {
         if (!f.aug && !d_mu) BAD("this shape has no ones row: the case must give mu");
         launch_wcov_mfma(d_X, d_w, d_idx, (int)m, d_mu, d_S, d_part, (int)B, (int)cs, (int)K, (int)ksplit, (int)sel_batch, dp[0], dp[1], d_active, s, d_rs,
                          want_mu ? d_muo : nullptr, (want_mu && A[9].count) ? d_u : nullptr, d_wsum, d_cost, d_cost ? d_cmin : nullptr, dp[2], d_shift);
-        outs = {{0, (size_t)(B * cs * cs), d_S}, {0, (size_t)(B * cs), d_muo}, {0, (size_t)(B * cs), d_u}, {2, (size_t)B, d_cmin, false}};
+        outs = {{0, (size_t)(B * cs * cs), d_S}, {0, (size_t)(B * cs), d_muo}, {0, (size_t)(B * cs), d_u}, {2, (size_t)B, d_cmin, false},
+                {0, wcov_mfma_workspace_doubles((int)B, (int)cs, (int)ksplit), d_part, false}};
     } else if (op == OP_SHRINK) {
         const long long cs = ip[0], m = ip[1], kind = ip[2];
         if (cs < 1 || cs > 800 || m < 2 || kind < 0 || kind > 3) BAD("case out of range");
