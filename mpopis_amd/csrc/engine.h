@@ -206,6 +206,10 @@ hipError_t launch_env_query(const EnvDesc& env, const double* x, const int* t, c
 // kernels_sample.hip
 void launch_sample_normal(double* Z, int B, int cs, int K, int as, int mppi_order, const uint64_t* seeds,
                           uint32_t slo, uint32_t shi, const double* dscale, const int* active, hipStream_t s, const double* rng_tab);
+// which kernel launch_sample_normal runs: four normals per Philox call (G order, 4 | cs), two (the members of a draw pair sit in adjacent rows: cs
+// even in G order, as even in :mppi order), or one normal per thread
+enum SampleNormalForm { SAMPLE_NORMAL_SINGLE = 0, SAMPLE_NORMAL_PAIR = 1, SAMPLE_NORMAL_QUAD = 2 };
+SampleNormalForm sample_normal_form(int cs, int as, int mppi_order);
 void launch_rng_tab_init(double* gtab, hipStream_t s);      // philox.h: kRngTabDoubles doubles (Box-Muller tables), once per handle
 void launch_sample_resample_draws(int32_t* di, double* du, int B, int K, const uint64_t* seeds, uint32_t slo, uint32_t shi,
                                   const int* active, hipStream_t s);

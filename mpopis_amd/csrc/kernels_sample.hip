@@ -10,11 +10,22 @@
 
 namespace mpopis {
 
+// log c for a table node c in [1/2, 1] (few fraction bits: c - 1 and c + 1 are exact) as 2 atanh(s), s = (c - 1)/(c + 1) <= 1/3 carried as
+// sh + sl: the series' tail s^3 (1/3 + s^2/5 + ...) is <= 4 % of s, so its rounding stays below 0.1 ulp of the sum, which rounds once.  The device
+// library's log() left 80 of the 256 entries off the correctly rounded value, the worst by 1.4 ulp (tests/test_gpu_sample_harness.py).
+__device__ double rng_tab_log(double c) {
+    const double num = c - 1.0, den = c + 1.0;
+    const double sh = num / den, sl = fma(-sh, den, num) / den;
+    const double z = sh * sh;
+    double p = 0.0;
+    for (int n = 20; n >= 1; --n) p = fma(p, z, 1.0 / (2 * n + 1));          // (1/9)^20 / 43: nothing is left
+    return 2.0 * (sh + fma(sh * z, p, sl));
+}
 __global__ void k_rng_tab_init(double* g_rng_tab) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < kRngTabLog) {
         const double c = (i == kRngTabLog - 1) ? 1.0 : 0.5 * (1.0 + (i + 0.5) / kRngTabLog);
-        g_rng_tab[2 * i] = 1.0 / c; g_rng_tab[2 * i + 1] = log(c);
+        g_rng_tab[2 * i] = 1.0 / c; g_rng_tab[2 * i + 1] = rng_tab_log(c);
     } else if (i < kRngTabLog + kRngTabSc) {
         const int j = i - kRngTabLog;
         g_rng_tab[2 * i] = sinpi((2.0 * j + 1.0) / kRngTabSc); g_rng_tab[2 * i + 1] = cospi((2.0 * j + 1.0) / kRngTabSc);
@@ -89,13 +100,18 @@ __global__ void __launch_bounds__(256) k_sample_normal_quad(double* __restrict__
 
 void launch_sample_normal(double* Z, int B, int cs, int K, int as, int mppi_order, const uint64_t* seeds,
                           uint32_t slo, uint32_t shi, const double* dscale, const int* active, hipStream_t s, const double* rng_tab) {
-    const bool pairable = mppi_order ? (as % 2 == 0) : (cs % 2 == 0);
-    if (!mppi_order && cs % 4 == 0)
+    const SampleNormalForm form = sample_normal_form(cs, as, mppi_order);
+    if (form == SAMPLE_NORMAL_QUAD)
         hipLaunchKernelGGL(k_sample_normal_quad, dim3((K + 255) / 256, cs / 4, B), dim3(256), 0, s, Z, cs, K, seeds, slo, shi, dscale, active, rng_tab);
-    else if (pairable)
+    else if (form == SAMPLE_NORMAL_PAIR)
         hipLaunchKernelGGL(k_sample_normal_pair, dim3((K + 255) / 256, cs / 2, B), dim3(256), 0, s, Z, cs, K, as, mppi_order, seeds, slo, shi, dscale, active, rng_tab);
     else
         hipLaunchKernelGGL(k_sample_normal, dim3((K + 255) / 256, cs, B), dim3(256), 0, s, Z, cs, K, as, mppi_order, seeds, slo, shi, dscale, active, rng_tab);
+}
+SampleNormalForm sample_normal_form(int cs, int as, int mppi_order) {
+    const bool pairable = mppi_order ? (as % 2 == 0) : (cs % 2 == 0);
+    if (!mppi_order && cs % 4 == 0) return SAMPLE_NORMAL_QUAD;
+    return pairable ? SAMPLE_NORMAL_PAIR : SAMPLE_NORMAL_SINGLE;
 }
 
 // resampling draws for :pmcmppi (rand(rng, Categorical(ws), K), :805): i uniform in [0,K), u in [0,1)

@@ -29,7 +29,10 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 // round 4: 256 / 128 entries (6 KB of LDS), |r| <= 2^-9 / |x| <= 0.0246, two Horner steps less in log1p and one less in each of sin and cos --
 // same accuracy class (every normal within 1e-13 of the libm evaluation, tests/test_gpu_parity.py; the top log interval is exact at u -> 1,
 // where sqrt(-2 log u) is most sensitive).  Table: kRngTabLog x {1/c_i, log c_i}, c_i = (1 + (i + 0.5)/kRngTabLog)/2 (last entry: c = 1),
-// then kRngTabSc x {sin, cos}(2 pi (j + 0.5)/kRngTabSc); filled once per handle by k_rng_tab_init with the library's correctly rounded functions.
+// then kRngTabSc x {sin, cos}(2 pi (j + 0.5)/kRngTabSc); filled once per handle by k_rng_tab_init: 1/c, sin and cos with the library's division, sinpi
+// and cospi (measured on the MI355X: every entry correctly rounded), log c with rng_tab_log of kernels_sample.hip (within 0.51 ulp, 4 of the 256
+// entries not correctly rounded; the library's log() was up to 1.4 ulp off).  tests/test_gpu_sample_harness.py holds every entry to 1 ulp and the
+// last log entry to exactly (1, 0), and every normal to a bound derived from the terms named below (tests/helpers/sample_cases.py).
 constexpr int kRngTabLog = 256, kRngTabSc = 128, kRngTabDoubles = 2 * (kRngTabLog + kRngTabSc);
 
 // log(u) for a normal-range u in (0, 1)
@@ -48,8 +51,8 @@ __device__ __forceinline__ double log_unit(double u, const double* __restrict__ 
 
 // (sin, cos)(2 pi u) for u = (w + 0.5) 2^-32 straight from one Philox word: sector j = top 7 bits, x = 2 pi (frac - 0.5)/128 (exact), degree-5 /
 // degree-6 Taylor kernels on |x| <= 0.0246 (next terms: x^7/5040 <= 1.1e-15 x relative 4.3e-14 ... see below; x^8/40320 <= 3.3e-18) and one
-// rotation by the tabulated sector centre.  The sine's truncation is 4.3e-14 RELATIVE TO x, i.e. <= 1.1e-15 absolute: half an ulp of the
-// rotated result, whose magnitude is O(1) except within 1e-15 of the axes.
+// rotation by the tabulated sector centre.  The sine's truncation is 4.3e-14 RELATIVE TO x, i.e. <= 1.1e-15 absolute: 5 ulp of a rotated result
+// of magnitude one, and the largest term of a normal's error (R times it: the worst normal measured is 33 ulp of 1 = 7.4e-15 off, at R = 6.7).
 __device__ __forceinline__ void sincos_2pi_u32(uint32_t w, const double* __restrict__ tab, double* sn, double* cs) {
     const int j = w >> 25;
     const double f = fma((double)(w & 0x1ffffffu), 0x1p-25, 0x1p-26 - 0.5);      // 128 u - j - 0.5, exact
