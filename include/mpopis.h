@@ -71,7 +71,11 @@ extern "C" {
  *    Later gained ONE more entry point, mpopis_get_plan: the control sequence the last policy step chose, the states it predicts, and the step's
  *    highest-weight sample rollouts, read out on request from what is still resident after the step.  mpopis_config and every other entry point
  *    are unchanged, and a handle that never calls it allocates and launches nothing new; a library that predates it does not export the
- *    symbol, which is how a caller detects support. */
+ *    symbol, which is how a caller detects support.
+ *    Later gained ONE more entry point, mpopis_run_trials_traced, and the struct mpopis_trace it takes: the closed loop of mpopis_run_trials that
+ *    also records each step's driven state, reward, iteration count, lane / β read-out and, every plan_every steps, the plan of mpopis_get_plan,
+ *    all from inside the resident loop.  mpopis_config and every other entry point are unchanged, mpopis_run_trials enqueues what it enqueued
+ *    before; a library that predates it does not export the symbol, which is how a caller detects support. */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -340,6 +344,49 @@ int  mpopis_get_plan(mpopis_handle *h, int32_t top, double *controls /* B*cs */,
 int  mpopis_set_state_noise(mpopis_handle *h, double sigma_x, double sigma_y, double sigma_psi);
 int  mpopis_run_trials(mpopis_handle *h, int32_t num_steps, int32_t laps, double *records /* B*16 */,
                        double *actions /* NULL or B x (num_steps+1) x as */);
+
+/* mpopis_run_trials that also records the run: where every slot's env stood at each MPC step, what the step earned, where the violations
+ * happened, and what the controller intended -- what plot_steps / save_gif / plot_traj of src/examples/car_example.jl draw and the per-step
+ * rew, v, β its trial loop keeps.  Everything is recorded on the device from inside the resident loop (no host round trip per step, the host
+ * still looks at the batch every eighth step) and downloaded once, at the end of the call.
+ * S = num_steps + 1 MPC steps per slot at the most; num_cars = 1 on the envs that are no car env.
+ *   plan_every   0: no plans.  p > 0: the plan of the MPC steps s = 0, p, 2p, ... <= num_steps; nplans = num_steps / p + 1
+ *   top          0 .. min(K, MPOPIS_PLAN_MAX_TOP): that many best samples beside each recorded plan
+ *   states       B x (S+1) x ss   [s] the state MPC step s started from, [s+1] the state after env(act) and the state noise
+ *   rewards      B x S            reward(env) after step s: the terms mpopis_run_trials sums into records[0]
+ *   iters        B x S            AIS iterations step s executed
+ *   within       B x S            as mpopis_env_query on states[s+1]
+ *   dist, beta   B x S x num_cars as mpopis_env_query on states[s+1] (0 on the envs for which mpopis_env_query returns none)
+ *   plan_controls B x nplans x cs, plan_traj B x nplans x (top+1) x (H x ss), plan_cost B x nplans x (top+1), plan_idx0 B x nplans x top,
+ *   plan_weights B x nplans x top: entry j is the plan of MPC step j * plan_every -- the fields of mpopis_get_plan, same meaning, same layout
+ *                                 per entry
+ * Any pointer may be NULL; what is not asked for is neither computed nor stored.
+ * A slot that executed n_b = records[b][1] + 1 MPC steps has its entries s < n_b filled (states: s <= n_b) and its plans j * plan_every < n_b;
+ * everything past them is zero, like `actions`.  A recorded plan is what mpopis_get_plan(top) returns when called right after that step's policy
+ * step and before its env step, bit for bit in every field.  records and actions are the bits mpopis_run_trials returns for the same handle,
+ * seed and arguments, whatever the trace asks for; trace == NULL is exactly mpopis_run_trials.  A run that ends on an error status returns what
+ * was recorded up to the step at which the host saw it; the return code is that of mpopis_run_trials.
+ * MPOPIS_ERR_ARG (reason in mpopis_last_error, handle unchanged): plan_every < 0, top out of range, top > 0 or a plan pointer set with
+ * plan_every == 0, and anything mpopis_run_trials refuses.  The trace lives in device memory for the length of the call --
+ *   8 B [(S+1) ss + S (2 + 2 num_cars)] + 8 B cs (top+1) + 8 nplans B [cs + (top+1)(H ss + 1) + 1.5 top] bytes at the most, plus the largest
+ *   plan field once more for the copy-out (only what is asked for is allocated) --
+ * MPOPIS_ERR_HIP when that cannot be allocated; the handle stays usable.  Like mpopis_run_trials the call ends the source of mpopis_get_plan. */
+typedef struct {
+    int32_t plan_every;
+    int32_t top;
+    double  *states;
+    double  *rewards;
+    int32_t *iters;
+    int32_t *within;
+    double  *dist, *beta;
+    double  *plan_controls;
+    double  *plan_traj;
+    double  *plan_cost;
+    int32_t *plan_idx0;
+    double  *plan_weights;
+} mpopis_trace;
+int  mpopis_run_trials_traced(mpopis_handle *h, int32_t num_steps, int32_t laps, double *records, double *actions,
+                              const mpopis_trace *trace /* NULL: exactly mpopis_run_trials */);
 
 /* ---- the one collective: summary records to rank 0 over RCCL/xGMI ---------------------
  * Trials shard over GPUs at trial granularity: trial k -> rank (k-1) mod G (`for k in 1:num_trials`,

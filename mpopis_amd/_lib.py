@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "mpopis_timing_reset", "mpopis_bench_policy_steps",
     "mpopis_create_custom", "mpopis_set_env_table", "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
     "mpopis_set_slot_hyper", "mpopis_get_slot_hyper", "mpopis_set_Sigma_slots", "mpopis_set_env_params_slots", "mpopis_set_tracks",
-    "mpopis_get_plan",
+    "mpopis_get_plan", "mpopis_run_trials_traced",
 ]
 
 
@@ -46,6 +46,15 @@ class Config(C.Structure):
 
 class Noise(C.Structure):
     _fields_ = [("Z", C.POINTER(C.c_double)), ("res_i0", C.POINTER(C.c_int32)), ("res_u", C.POINTER(C.c_double))]
+
+
+class Trace(C.Structure):
+    """mpopis_trace: what mpopis_run_trials_traced records (NULL pointers: not asked for)."""
+    _fields_ = [("plan_every", C.c_int32), ("top", C.c_int32),
+                ("states", C.POINTER(C.c_double)), ("rewards", C.POINTER(C.c_double)), ("iters", C.POINTER(C.c_int32)),
+                ("within", C.POINTER(C.c_int32)), ("dist", C.POINTER(C.c_double)), ("beta", C.POINTER(C.c_double)),
+                ("plan_controls", C.POINTER(C.c_double)), ("plan_traj", C.POINTER(C.c_double)), ("plan_cost", C.POINTER(C.c_double)),
+                ("plan_idx0", C.POINTER(C.c_int32)), ("plan_weights", C.POINTER(C.c_double))]
 
 
 class MPOPISError(RuntimeError):
@@ -83,8 +92,10 @@ def lib():
         if hasattr(L, "mpopis_set_env_params_slots"):           # (per-slot env parameters and tracks: newer still)
             L.mpopis_set_env_params_slots.argtypes = [H, _dp, C.c_int32]
             L.mpopis_set_tracks.argtypes = [H, C.c_int32, _ip, _dp, _dp, _dp, _ip]
-        if hasattr(L, "mpopis_get_plan"):                       # (the plan read-out: newest)
+        if hasattr(L, "mpopis_get_plan"):                       # (the plan read-out)
             L.mpopis_get_plan.argtypes = [H, C.c_int32, _dp, _dp, _dp, _ip, _dp]
+        if hasattr(L, "mpopis_run_trials_traced"):              # (the traced closed loop: newest)
+            L.mpopis_run_trials_traced.argtypes = [H, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(Trace)]
         L.mpopis_destroy.argtypes = [H]
         L.mpopis_destroy.restype = None
         L.mpopis_set_env_params.argtypes = [H, _dp, C.c_int32]

@@ -325,9 +325,22 @@ void launch_alias_sample(const double* accept, const int32_t* alias, const int32
 
 // kernels_plan.hip (mpopis_get_plan): the top samples of a weight row in the order "weight descending, index ascending" (top <= min(K, MPOPIS_PLAN_MAX_TOP);
 // idx / wsel [B][top]), then controls [B][cs] = Uin + wn and the noise block Eplan [B][cs][top + 1]: column 0 = wn, column j = E[:, idx[j-1]] + (Ucur - Uin)
-void launch_plan_select(const double* w, int B, int K, int top, int32_t* idx, double* wsel, hipStream_t s);
+// active (nullable, [B]): slots with active == 0 write nothing
+void launch_plan_select(const double* w, int B, int K, int top, int32_t* idx, double* wsel, hipStream_t s, const int* active = nullptr);
 void launch_plan_assemble(const double* E, const double* Ucur, const double* Uin, const double* wn, const int32_t* idx, int B, int cs, int K, int top,
-                          double* controls, double* Eplan, hipStream_t s);
+                          double* controls, double* Eplan, hipStream_t s, const int* active = nullptr);
+
+// kernels_trace.hip (mpopis_run_trials_traced): the per-step record of the closed loop, written straight into the ABI's
+// slot-major arrays (S = num_steps + 1 entries per slot; any pointer may be null), and the reordering of the step-major plan buffers for the copy-out
+struct TraceStepOut { double *states, *rewards, *dist, *beta; int32_t *iters, *within; };
+// states[b][0] = x[b] for every slot
+void launch_trace_start(const double* x, double* states, int B, int ss, int S, hipStream_t s);
+// Slots whose step counter cnt[b * cnt_stride] equals step + 1 -- those that were alive during MPC step `step` -- record states[b][step + 1] = x[b],
+// rewards / iters [b][step], and within / dist / beta [b][step] of x[b] as mpopis_env_query computes them (car env; other envs: within = 1)
+void launch_trace_step(int env_kind, int ncars, int ss, const Track& tk, const Track* slot_tk, const double* x, const double* reward, const int* iters,
+                       const double* cnt, int cnt_stride, int step, int S, const TraceStepOut& out, int B, hipStream_t s);
+// out[b][j][0..per) = in[j][b][0..per) for j < J, b < B; elem_bytes 4 or 8
+void launch_trace_reorder(const void* in, void* out, int B, int J, size_t per, int elem_bytes, hipStream_t s);
 
 // kernels_cma.hip
 // kernels_invsqrt.hip: y = A^-1/2 b (Lanczos + quadrature) and fro = tr(A^-1) = scale * ||L^-1||_F^2 with L = chol(scale * A)

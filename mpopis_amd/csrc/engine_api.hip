@@ -1174,6 +1174,12 @@ int mpopis_run_trials(mpopis_handle* h, int32_t num_steps, int32_t laps, double*
     return h->run_trials(num_steps, laps, records, actions);
 }
 
+int mpopis_run_trials_traced(mpopis_handle* h, int32_t num_steps, int32_t laps, double* records, double* actions, const mpopis_trace* trace) {
+    if (h) h->plan_drop("mpopis_run_trials_traced");
+    if (!h || !records) return MPOPIS_ERR_ARG;
+    return h->run_trials(num_steps, laps, records, actions, trace);
+}
+
 int mpopis_set_overlap(mpopis_handle* h, int32_t on) {
     if (h) h->plan_drop("mpopis_set_overlap");
     if (!h) return MPOPIS_ERR_ARG;
@@ -1310,6 +1316,13 @@ void mpopis_handle::shift_slots(ptrdiff_t db) {
     mv(S0.Sigma, (ptrdiff_t)S0stride); mv(S0.L, (ptrdiff_t)S0stride); mv(S0.Lp, (ptrdiff_t)P0stride); mv(S0.nesA, (ptrdiff_t)S0stride); mv(S0.nesS, (ptrdiff_t)S0stride);   // per-slot pol.Σ (stride 0: shared)
     mv(custom.table_view, (ptrdiff_t)custom.table_stride);                     // a custom env's per-slot tables (stride 0: one shared table)
     mv(d_actlog, actlog_stride);                                               // run_trials' action log of the current call
+    if (trace.base) {                                                          // ... and its trace
+        const ptrdiff_t S = trace.S, W = trace.top + 1;
+        mv(trace.step.states, (S + 1) * ss); mv(trace.step.rewards, S); mv(trace.step.iters, S); mv(trace.step.within, S);
+        mv(trace.step.dist, S * trace.ncars); mv(trace.step.beta, S * trace.ncars);
+        mv(trace.E, (ptrdiff_t)cs * W); mv(trace.controls, (ptrdiff_t)cs); mv(trace.traj, W * ss * T); mv(trace.cost, W);
+        mv(trace.w, (ptrdiff_t)trace.top); mv(trace.idx, (ptrdiff_t)trace.top);
+    }
 }
 
 // pol(env) for all slots.  With >= 2 slots the batch may be split into parts that run as independent chains on

@@ -137,6 +137,22 @@ struct mpopis_handle {
     // Level-3 harness
     double* d_hs = nullptr; int* d_alive = nullptr; const int* alive_gate = nullptr; bool status_sticky = false;
     double* d_actlog = nullptr; ptrdiff_t actlog_stride = 0;   // run_trials' action log of the current call ([B][num_steps + 1][as]) and its slot stride
+    // mpopis_run_trials_traced: the trace of the current call, ONE allocation that lives as long as d_actlog does; every
+    // pointer is that of the handle's first slot and moves with the slot views (shift_slots), null while not asked for.  The step fields have
+    // the ABI's slot-major layout ([B][S + 1][ss], [B][S], [B][S][ncars]).  The plan fields are step-major -- [nplans][B_full][per slot], so that
+    // the plan kernels and the rollout write a step's slice in place with their own strides: entry j of a part starts j * B_full slots further
+    // on -- and are reordered into `stage` at the copy-out; E is the noise block of ONE step ([B][cs][top + 1]: a part's steps follow each other
+    // on its stream).
+    struct TraceBufs {
+        void* base = nullptr;
+        int plan_every = 0, top = 0, nplans = 0, S = 0, ncars = 1;
+        mpopis::TraceStepOut step{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        double *E = nullptr, *controls = nullptr, *traj = nullptr, *cost = nullptr, *w = nullptr; int32_t* idx = nullptr;
+        void* stage = nullptr;
+    } trace;
+    int trace_reserve(const mpopis_trace& tr, int num_steps);  // engine_harness.hip; sets err
+    void trace_plan(int j);                                    // plan j of the current part's slots, between its policy step and its env step
+    int trace_download(const mpopis_trace& tr);
     double noise_sx = 0.0, noise_sy = 0.0, noise_spsi = 0.0;   // simulate_car_racing state noise (car_example.jl:224-236)
     // RCCL communicator for the summary gather (engine_comm.hip); world == 1 needs none
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;
@@ -210,7 +226,7 @@ struct mpopis_handle {
         return st;
     }
     int ais_update(int n, bool injected);
-    int run_trials(int num_steps, int laps, double* records, double* actions);
+    int run_trials(int num_steps, int laps, double* records, double* actions, const mpopis_trace* tr = nullptr);
     void init_cma_constants();
     void cma_begin();
     const double* cma_sigma2();

@@ -1,6 +1,7 @@
 // kernels_plan.hip -- the read-out behind mpopis_get_plan: which samples of the last step carry the most weight, and the
 // control sequences of the plan and of those samples as one [B][cs][top + 1] noise block that the rollout kernels take as they take E.
-// Nothing here runs during a policy step.
+// Nothing here runs during a policy step.  mpopis_run_trials_traced launches the same kernels between a policy step and its env step, on the part's
+// slots, with active = the harness' alive flags.
 #include "engine.h"
 
 namespace mpopis {
@@ -14,8 +15,10 @@ __device__ __forceinline__ bool plan_key_less(const PlanKey& a, const PlanKey& b
 // the row for the largest key strictly below the one round j - 1 took, the lanes of a wave reduce by shuffles, the waves through one LDS row
 // (two rows in turn: one barrier per round).  No scratch, no marking of taken samples, no atomics: equal weights cost nothing extra.
 template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_plan_select(const double* __restrict__ w, int K, int top, int32_t* __restrict__ idx, double* __restrict__ wsel) {
+__global__ void __launch_bounds__(BLOCK) k_plan_select(const double* __restrict__ w, int K, int top, int32_t* __restrict__ idx, double* __restrict__ wsel,
+                                                       const int* __restrict__ active) {
     MPOPIS_HI_PRIO();
+    if (active && !active[blockIdx.x]) return;                                 // (the traced closed loop: a frozen slot's stale weights stay out of the trace)
     constexpr int NW = BLOCK / 64;
     __shared__ unsigned long long sh_bits[2][NW];
     __shared__ unsigned sh_lo[2][NW];
@@ -55,9 +58,10 @@ __global__ void __launch_bounds__(BLOCK) k_plan_select(const double* __restrict_
 // U_orig: column 0 the weighted noise itself, column j the sample's noise after the final shift, formed like k_transpose_out forms E_out.
 __global__ void __launch_bounds__(256) k_plan_assemble(const double* __restrict__ E, const double* __restrict__ Ucur, const double* __restrict__ Uin,
                                                        const double* __restrict__ wn, const int32_t* __restrict__ idx, int cs, int K, int top,
-                                                       double* __restrict__ controls, double* __restrict__ Eplan) {
+                                                       double* __restrict__ controls, double* __restrict__ Eplan, const int* __restrict__ active) {
     MPOPIS_HI_PRIO();
     const int b = blockIdx.y, W = top + 1;
+    if (active && !active[b]) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= cs * W) return;
     const int r = i / W, j = i - r * W;
@@ -73,15 +77,15 @@ __global__ void __launch_bounds__(256) k_plan_assemble(const double* __restrict_
     Eplan[br * W + j] = v;
 }
 
-void launch_plan_select(const double* w, int B, int K, int top, int32_t* idx, double* wsel, hipStream_t s) {
+void launch_plan_select(const double* w, int B, int K, int top, int32_t* idx, double* wsel, hipStream_t s, const int* active) {
     if (top < 1) return;
-    if (K > 1024) hipLaunchKernelGGL(k_plan_select<1024>, dim3(B), dim3(1024), 0, s, w, K, top, idx, wsel);
-    else hipLaunchKernelGGL(k_plan_select<256>, dim3(B), dim3(256), 0, s, w, K, top, idx, wsel);
+    if (K > 1024) hipLaunchKernelGGL(k_plan_select<1024>, dim3(B), dim3(1024), 0, s, w, K, top, idx, wsel, active);
+    else hipLaunchKernelGGL(k_plan_select<256>, dim3(B), dim3(256), 0, s, w, K, top, idx, wsel, active);
 }
 
 void launch_plan_assemble(const double* E, const double* Ucur, const double* Uin, const double* wn, const int32_t* idx, int B, int cs, int K, int top,
-                          double* controls, double* Eplan, hipStream_t s) {
-    hipLaunchKernelGGL(k_plan_assemble, dim3((cs * (top + 1) + 255) / 256, B), dim3(256), 0, s, E, Ucur, Uin, wn, idx, cs, K, top, controls, Eplan);
+                          double* controls, double* Eplan, hipStream_t s, const int* active) {
+    hipLaunchKernelGGL(k_plan_assemble, dim3((cs * (top + 1) + 255) / 256, B), dim3(256), 0, s, E, Ucur, Uin, wn, idx, cs, K, top, controls, Eplan, active);
 }
 
 }  // namespace mpopis

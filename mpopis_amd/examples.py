@@ -156,7 +156,7 @@ def _apply_per_trial(eng, per, cov_slots, policy):
 def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="cemppi", laps=2, num_samples=150, horizon=50,
                         λ=10.0, α=1.0, U0=None, cov_mat=None, ais_its=10, λ_ais=20.0, ce_elite_threshold=0.8, ce_Σ_est="ss",
                         cma_σ=0.75, cma_elite_threshold=0.8, state_x_sigma=0.0, state_y_sigma=0.0, state_ψ_sigma=0.0,
-                        seed=None, log_runs=True, device=0, dist=None, quiet=False, track="curve", car_params=None):
+                        seed=None, log_runs=True, device=0, dist=None, quiet=False, track="curve", car_params=None, trace=None):
     """Returns (records, summary) on rank 0 (None elsewhere).  Differences from the reference harness, all
     forced by the platform: plotting/GIF options are not offered (out of scope); the state noise (single car only,
     car_example.jl:224-236) is drawn from the trial's device stream instead of the env's MersenneTwister.
@@ -165,7 +165,10 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
     track: a bundled name (engine.BUNDLED_TRACKS) or an (x, y, w) triple, or a sequence of num_trials of either -- a policy over several tracks
     in one resident batch, every distinct track uploaded once (split_tracks_per_trial).  car_params: the 20 values of CarRacingEnvParams + dt, δt
     (include/mpopis.h), or (num_trials, 20) for one vector per trial (split_env_params_per_trial).
-    ce_Σ_est defaults to :ss like the reference (car_example.jl:66); :mle is the other supported estimator."""
+    ce_Σ_est defaults to :ss like the reference (car_example.jl:66); :mle is the other supported estimator.
+    trace: as Engine.run_trials takes it (True, or dict(plan_every, top[, fields])) -- the run is recorded on the device, what plot_steps /
+    save_gif / plot_traj of the reference draw, and the call returns (records, summary, trace) with the trace of THIS rank's trials in slot
+    order (trial ids: shard_trials; traces are not gathered; an empty dict on a rank without trials)."""
     pt = str(policy_type).lstrip(":")
     rank = dist.get_rank() if (dist is not None and dist.is_initialized()) else 0
     world = dist.get_world_size() if (dist is not None and dist.is_initialized()) else 1
@@ -193,6 +196,8 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
                  cma_sigma=cma_σ, seed=seed, device=device, cov=cov_shared, U0=U0,
                  track=None if trk_shared is None else _resolve_track(trk_shared), env_params=par_shared)
     r = np.zeros((0, RECORD_LEN))
+    tr_out = {}
+    traced = (lambda *res: res + (tr_out,)) if not (trace is None or trace is False) else (lambda *res: res)
     if mine:
         _apply_per_trial(eng, {k: v[1] for k, v in split.items()}, cov_slots, pt)
         if trk_slots is not None:
@@ -201,7 +206,10 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
             eng.set_env_params_slots(par_slots)
         eng.seed_slots([seed + k for k in mine])
         eng.set_state_noise(state_x_sigma, state_y_sigma, state_ψ_sigma)
-        r = eng.run_trials(num_steps, laps)
+        if trace is None or trace is False:
+            r = eng.run_trials(num_steps, laps)
+        else:
+            r, tr_out = eng.run_trials(num_steps, laps, trace=trace)
     ex_time = time.time() - t0                 # Ex Time of this rank's batch (its trials run concurrently)
     n_max = (num_trials + world - 1) // world
     if world > 1 and dist.get_backend() == "nccl":
@@ -212,14 +220,14 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
         parts = eng.gather_summary(r, n_max)
         eng.close()
         if parts is None:
-            return None, None
+            return traced(None, None)
         allrec = assemble_gathered(parts, world)
     else:
         eng.close()
         rec = np.array([np.concatenate([[k], r[i], [ex_time]]) for i, k in enumerate(mine)]).reshape(-1, RECORD_LEN + 2)
         allrec = _gather_records(rec, dist)
     if allrec is None:
-        return None, None
+        return traced(None, None)
     allrec = allrec[np.argsort(allrec[:, 0])]
     cols = [1, 2, 3] + [4 + i for i in range(laps)] + [8, 9, 10, 11, 12, 13] + ([14] if num_cars > 1 else []) + [allrec.shape[1] - 1]
     table = allrec[:, cols]
@@ -235,12 +243,12 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
         print("-----------------------------------")
         for name in ("AVE", "STD", "MED", "L95", "U95", "MIN", "MAX"):
             print("Trials %3s: " % name + " : ".join("%12.2f" % v if i in (0, 2) else "%7.2f" % v for i, v in enumerate(summ[name])))
-    return allrec, summ
+    return traced(allrec, summ)
 
 
 def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cemppi", num_samples=20, horizon=15, λ=0.1, α=1.0, U0=(0.0,),
                          cov_mat=(1.5,), ais_its=5, λ_ais=0.1, ce_elite_threshold=0.8, ce_Σ_est="mle", cma_σ=0.75,
-                         cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None):
+                         cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None):
     pt = str(policy_type).lstrip(":")
     par_shared, par_slots = split_env_params_per_trial(env_params, 11 if env_kind == "cartpole" else 8, num_trials)
     if seed is None:
@@ -259,7 +267,8 @@ def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cem
     if x0 is not None:
         eng.set_state(np.asarray(x0, dtype=np.float64).reshape(num_trials, ss))
     t0 = time.time()
-    rec = eng.run_trials(num_steps, 0)
+    traced = not (trace is None or trace is False)
+    rec, tr_out = eng.run_trials(num_steps, 0, trace=trace) if traced else (eng.run_trials(num_steps, 0), None)
     ex = time.time() - t0
     eng.close()
     table = np.concatenate([rec[:, :3], np.full((num_trials, 1), ex)], 1)
@@ -271,18 +280,18 @@ def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cem
         print("-----------------------------------")
         for name in ("AVE", "STD", "MED", "L95", "U95", "MIN", "MAX"):
             print("Trials %3s: %12.2f : %7.2f: %12.2f : %7.2f" % ((name,) + tuple(summ[name])))
-    return rec, summ
+    return (rec, summ, tr_out) if traced else (rec, summ)
 
 
 _SIMPLE_KW = dict(num_trials=1, num_steps=200, policy_type="cemppi", num_samples=20, horizon=15, λ=0.1, α=1.0, U0=(0.0,),
                   cov_mat=(1.5,), ais_its=5, λ_ais=0.1, ce_elite_threshold=0.8, ce_Σ_est="mle", cma_σ=0.75,
-                  cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None)
+                  cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None)
 
 
 def simulate_mountaincar(**kw):
     """mountaincar_example.jl:49-207 (same keyword arguments and defaults); x0: per-trial start positions
     (the reference draws x ~ U(-0.6,-0.4) from an unseeded RNG; default here -0.5).  env_params: the 8 values include/mpopis.h lists for
-    MountainCar, or (num_trials, 8) for one vector per trial."""
+    MountainCar, or (num_trials, 8) for one vector per trial.  trace: as simulate_car_racing; the call then returns (records, summary, trace)."""
     a = dict(_SIMPLE_KW); _check_kw(a, kw); a.update(kw)
     if a["x0"] is not None:
         x = np.asarray(a["x0"], dtype=np.float64).reshape(a["num_trials"])
@@ -294,7 +303,7 @@ def simulate_cartpole(**kw):
     """cartpole_example.jl:8-190 (same keyword arguments and defaults); x0: (num_trials, 4) start states
     [x, xdot, theta, thetadot].  The reference draws 0.1*rand(4) - 0.05 from an unseeded MersenneTwister (:111);
     default here: the same box drawn from numpy's default_rng(seed + k).  env_params: the 11 values include/mpopis.h lists for CartPole, or
-    (num_trials, 11) for one vector per trial."""
+    (num_trials, 11) for one vector per trial.  trace: as simulate_car_racing; the call then returns (records, summary, trace)."""
     a = dict(_SIMPLE_KW); _check_kw(a, kw); a.update(kw)
     if a["seed"] is None:
         a["seed"] = int(np.random.default_rng().integers(1, 10 ** 10))
