@@ -203,6 +203,19 @@ hipError_t launch_env_step(const EnvDesc& env, double* x, int* t, int* done, con
 
 hipError_t launch_env_query(const EnvDesc& env, const double* x, const int* t, const int* done, double* reward, int* within, double* dist, double* beta, int B, hipStream_t s, const SlotEnv& senv = SlotEnv());
 
+// kernels_harness.hip: the bookkeeping of the closed-loop trial harness (mpopis_run_trials).  hs [B][kH_N]: the per-slot accumulator (doubles)
+enum { kH_rew = 0, kH_cnt, kH_lap, kH_prev_y, kH_trk, kH_beta, kH_crash, kH_vmean, kH_vmax, kH_bmean, kH_bmax,
+       kH_lap0, kH_lap1, kH_lap2, kH_lap3, kH_rollouts, kH_N = 16 };
+// state noise of the one-car env (car_example.jl:224-236): seeds == nullptr switches it off; rng_tab = the table of launch_rng_tab_init
+struct StateNoise { double sx, sy, spsi; const uint64_t* seeds; const double* rng_tab; };
+// hs = 0 (vmax = bmax = -inf), alive = 1
+void launch_harness_init(double* hs, int* alive, int B, hipStream_t s);
+// after env(act), for the slots with alive != 0: state noise, action log row `step` ([B][num_steps + 1][as], nullable), cnt += 1, rew += reward,
+// rollouts += iters K, the car statistics, violation counters, lap counter; alive = 0 when the trial ends
+void launch_harness_update(const EnvDesc& env, double* x, const int* done_env, const double* reward, const int* iters, double* hs, int* alive,
+                           const double* control, double* actlog, int step, int num_steps, int laps, int K, int B, const StateNoise& nz,
+                           const SlotEnv& senv, hipStream_t s);
+
 // kernels_sample.hip
 void launch_sample_normal(double* Z, int B, int cs, int K, int as, int mppi_order, const uint64_t* seeds,
                           uint32_t slo, uint32_t shi, const double* dscale, const int* active, hipStream_t s, const double* rng_tab);
