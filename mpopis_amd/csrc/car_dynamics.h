@@ -166,6 +166,30 @@ inline void build_track_ring(int P, const double* x, const double* y, const doub
     }
     for (int i = 0; i < P; ++i) { cert[i] = nd[(size_t)i * S + W]; cert[P + i] = ring_cert_radius2(P, x, y, i, 2); }
 }
+// host: everything a Track points to, in the four buffers mpopis_set_track uploads -- the one place that decides their layout.  The product
+// (engine_api.hip: upload_track), the kernel harnesses under tools/ and the host shim of the tests all build their Track through view().
+struct TrackHost {
+    int P = 0;
+    std::vector<double> xy;             // x | y | w | n2, P each
+    std::vector<double> nd;             // neighbour distances, build_track_tables
+    std::vector<int> ni;                // neighbour indices
+    std::vector<double> ring;           // the ring table, then the two certificates from cert_off on
+    size_t cert_off = 0;
+    TrackHost() = default;
+    TrackHost(int P_, const double* x, const double* y, const double* w) : P(P_), xy((size_t)4 * P_) {
+        for (int i = 0; i < P; ++i) { xy[i] = x[i]; xy[P + i] = y[i]; xy[2 * P + i] = w[i]; xy[3 * P + i] = x[i] * x[i] + y[i] * y[i]; }
+        std::vector<double> cert;
+        build_track_tables(P, x, y, nd, ni);
+        build_track_ring(P, x, y, w, xy.data() + 3 * P, nd, ring, cert);
+        cert_off = ring.size();
+        ring.insert(ring.end(), cert.begin(), cert.end());
+    }
+    // the Track over copies of the four buffers at these addresses (device or host)
+    Track view(const double* xy_, const int* ni_, const double* nd_, const double* ring_) const {
+        return Track{xy_, xy_ + P, xy_ + 2 * P, xy_ + 3 * P, P, ni_, nd_, std::min<int>(kTrackNbrW, P), ring_, ring_ + cert_off};
+    }
+    Track view() const { return view(xy.data(), ni.data(), nd.data(), ring.data()); }      // over this object's own buffers
+};
 
 // Rounding discipline of everything below: NO implicit a*b + c.  hipcc's default (-ffp-contract=fast, which this library is built with) lets the
 // BACKEND fuse a multiply into a dependent add wherever it finds one, per inlining context and whatever pragma is in force -- the same source

@@ -560,32 +560,18 @@ int mpopis_set_env_table(mpopis_handle* h, const double* data, int64_t n, int32_
     return MPOPIS_OK;
 }
 
-// one track to the device: x, y, w, |q|^2, the neighbour tables and the ring table with its certificates; *out = its descriptor
+// one track to the device: x, y, w, |q|^2, the neighbour tables and the ring table with its certificates (car_dynamics.h: TrackHost decides the
+// layout); *out = its descriptor
 static int upload_track(mpopis_handle* h, const double* x, const double* y, const double* w, int32_t P, Track* out) {
-    double* d = nullptr;
-    if (h->shared_alloc(d, (size_t)4 * P)) return MPOPIS_ERR_HIP;
-    std::vector<double> n2(P);
-    for (int i = 0; i < P; ++i) n2[i] = x[i] * x[i] + y[i] * y[i];
-    HIPCHK(h, hipMemcpyAsync(d + 3 * P, n2.data(), sizeof(double) * P, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d, x, sizeof(double) * P, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d + P, y, sizeof(double) * P, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d + 2 * P, w, sizeof(double) * P, hipMemcpyHostToDevice, h->stream));
-    // neighbour tables of the anchored nearest-point search (car_dynamics.h: build_track_tables)
-    const int W = std::min<int>(kTrackNbrW, P);
-    std::vector<double> nd; std::vector<int> ni;
-    build_track_tables(P, x, y, nd, ni);
-    double* dnd = nullptr; int* dni = nullptr;
-    if (h->shared_alloc(dnd, nd.size()) || h->shared_alloc(dni, ni.size())) return MPOPIS_ERR_HIP;
-    HIPCHK(h, hipMemcpyAsync(dnd, nd.data(), sizeof(double) * nd.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dni, ni.data(), sizeof(int) * ni.size(), hipMemcpyHostToDevice, h->stream));
-    std::vector<double> ring, cert;
-    build_track_ring(P, x, y, w, n2.data(), nd, ring, cert);
-    double* dring = nullptr;
-    if (h->shared_alloc(dring, ring.size() + cert.size())) return MPOPIS_ERR_HIP;
-    HIPCHK(h, hipMemcpyAsync(dring, ring.data(), sizeof(double) * ring.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dring + ring.size(), cert.data(), sizeof(double) * cert.size(), hipMemcpyHostToDevice, h->stream));
+    const TrackHost th(P, x, y, w);
+    double *d = nullptr, *dnd = nullptr, *dring = nullptr; int* dni = nullptr;
+    if (h->shared_alloc(d, th.xy.size()) || h->shared_alloc(dnd, th.nd.size()) || h->shared_alloc(dni, th.ni.size()) || h->shared_alloc(dring, th.ring.size())) return MPOPIS_ERR_HIP;
+    HIPCHK(h, hipMemcpyAsync(d, th.xy.data(), sizeof(double) * th.xy.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dnd, th.nd.data(), sizeof(double) * th.nd.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dni, th.ni.data(), sizeof(int) * th.ni.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dring, th.ring.data(), sizeof(double) * th.ring.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, wait_stream(h->stream));
-    *out = Track{d, d + P, d + 2 * P, d + 3 * P, P, dni, dnd, W, dring, dring + ring.size()};
+    *out = th.view(d, dni, dnd, dring);
     return MPOPIS_OK;
 }
 

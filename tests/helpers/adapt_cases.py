@@ -14,20 +14,16 @@ from the formulas in the two kernel files' headers and the oracle.  The error bo
   exp / sqrt / pow   the sum bound of ||p_sigma||^2 propagated to first order through the reference formula, + 8 u relative per library function
                      (the HIP math API reference lists 1 ULP for the double-precision exp, pow and sqrt: below 8 u = 4 ULP, so 8 u stands).
 A structural error -- a dropped column, a wrong row, a stale partial, a missing mirror -- moves an entry by about sum|terms| / n, 1e12 bounds away."""
-import struct
 import numpy as np
+from tests.helpers import harness_io as IO
+from tests.helpers.harness_io import F64, I32, GUARD, LD, U, bits, is_poison, split_guard                # (re-exported: the tests read them as A.<name>)
 
 OP_BREAK, OP_SCATTER, OP_POTRI, OP_UPDATE, OP_CMA_BEGIN, OP_CMA_PATHS, OP_CMA_SIGMA = range(7)
 OPS = ("BREAK", "SCATTER", "POTRI", "UPDATE", "CMA_BEGIN", "CMA_PATHS", "CMA_SIGMA")
 MAGIC_IN, MAGIC_OUT = b"ADPCASE1", b"ADPRES01"
-GUARD = 64
-F64, I32 = 0, 1
-_DT = {F64: np.float64, I32: np.int32}
 POISON_I32 = np.frombuffer(b"\xa5" * 4, dtype=np.int32)[0]
 POISON_F64_BITS = np.frombuffer(b"\xa5" * 8, dtype=np.uint64)[0]
 POISON_F64 = np.frombuffer(b"\xa5" * 8, dtype=np.float64)[0]
-U = 2.0 ** -53
-LD = np.longdouble
 ELEM = 16                                                  # roundings allowed to an elementwise formula (see above)
 LIBM = 8                                                   # u per exp / sqrt / pow
 # include/mpopis.h
@@ -86,68 +82,21 @@ CMA_SIGMA_CASES = [(cs, h) for cs in (1, 16, 17, 300) for h in (0, 1)]
 # ---- the harness's files ---------------------------------------------------------------------------------------------------------------------
 def pack_case(op, B, ipar, dpar, arrays):
     """arrays: list of (type, array or None) in the op's fixed order (None = not given)"""
-    out = [MAGIC_IN, struct.pack("<5q", op, B, len(ipar), len(dpar), len(arrays)), struct.pack("<%dq" % len(ipar), *[int(v) for v in ipar]),
-           struct.pack("<%dd" % len(dpar), *[float(v) for v in dpar])]
-    for t, a in arrays:
-        a = np.zeros(0, _DT[t]) if a is None else np.ascontiguousarray(a, dtype=_DT[t]).reshape(-1)
-        out += [struct.pack("<2q", t, a.size), a.tobytes()]
-    return b"".join(out)
+    return IO.pack_case(MAGIC_IN, op, B, ipar, dpar, arrays)
 
 
 def unpack_case(buf):
-    assert buf[:8] == MAGIC_IN
-    op, B, nI, nD, nA = struct.unpack_from("<5q", buf, 8)
-    off = 48
-    ipar = list(struct.unpack_from("<%dq" % nI, buf, off)); off += 8 * nI
-    dpar = list(struct.unpack_from("<%dd" % nD, buf, off)); off += 8 * nD
-    arrays = []
-    for _ in range(nA):
-        t, n = struct.unpack_from("<2q", buf, off); off += 16
-        a = np.frombuffer(buf, dtype=_DT[t], count=n, offset=off).copy(); off += a.nbytes
-        arrays.append((t, a))
-    assert off == len(buf)
-    return op, B, ipar, dpar, arrays
+    return IO.unpack_case(MAGIC_IN, buf)
 
 
 def pack_result(arrays):
     """what the harness writes (used by the CPU round-trip test); arrays: list of (type, array with its guard entries)"""
-    out = [MAGIC_OUT, struct.pack("<3q", 0, GUARD, len(arrays))]
-    for t, a in arrays:
-        a = np.ascontiguousarray(a, dtype=_DT[t]).reshape(-1)
-        out += [struct.pack("<2q", t, a.size), a.tobytes()]
-    return b"".join(out)
+    return IO.pack_result(MAGIC_OUT, 0, arrays)
 
 
 def unpack_result(buf):
     """-> [arrays as written, guard entries included]"""
-    assert buf[:8] == MAGIC_OUT, buf[:8]
-    _, guard, nA = struct.unpack_from("<3q", buf, 8)
-    assert guard == GUARD
-    off, arrays = 32, []
-    for _ in range(nA):
-        t, n = struct.unpack_from("<2q", buf, off); off += 16
-        a = np.frombuffer(buf, dtype=_DT[t], count=n, offset=off).copy(); off += a.nbytes
-        arrays.append(a)
-    assert off == len(buf), (off, len(buf))
-    return arrays
-
-
-def is_poison(a):
-    a = np.asarray(a)
-    if a.dtype == np.float64:
-        return a.view(np.uint64) == POISON_F64_BITS
-    return a == POISON_I32
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def split_guard(a, shape):
-    """-> (body reshaped, guard)"""
-    n = int(np.prod(shape))
-    assert a.size == n + GUARD, (a.size, n)
-    return a[:n].reshape(shape), a[n:]
+    return IO.unpack_result(MAGIC_OUT, buf)[1]
 
 
 def cm(flat, n):

@@ -26,13 +26,12 @@ F_ij = -1 / (sqrt(l_i) sqrt(l_j) (sqrt(l_i) + sqrt(l_j))), for x^1/2: 1 / (sqrt(
 second order, (kappa u)^2.  NumPy has no longdouble eigen-solver; this needs none.  The CPU file certifies each reference: Y symmetric positive
 definite with Y A Y = I to 1 / 100 of the case's tolerance (the SPD solution of Y A Y = I is unique)."""
 import functools
-import struct
 import numpy as np
+from tests.helpers import harness_io as IO
+from tests.helpers.harness_io import U64, is_poison                   # (re-exported)
 from tests.helpers.adapt_cases import (LD, U, F64, I32, GUARD, POISON_I32, POISON_F64, POISON_F64_BITS, OK, ERR_ARG, ERR_NOT_PD, ERR_ACTION, ERR_HIP,
                                        ERR_NUMERIC, bits, split_guard, cm, to_cm, sum_bound, status_rank, actives, potri_factor, potri_reference)
 
-U64 = 2
-_DT = {F64: np.float64, I32: np.int32, U64: np.uint64}
 MAGIC_IN, MAGIC_OUT = b"DNSCASE1", b"DNSRES01"
 OP_POTRF, OP_SOLVE, OP_GVEC, OP_TRTRI, OP_INVSQRT, OP_SYM_SQRT = range(6)
 POTRF_LDS, POTRF_REG, POTRF_COOP, POTRF_GLOBAL = range(4)
@@ -44,59 +43,22 @@ MAX_WG = 64                                                # MPOPIS_COOP_MAX_WG 
 SCALES = np.array([0.25, 1.0, 9.0])
 
 
-def is_poison(a):
-    a = np.asarray(a)
-    if a.dtype == np.float64:
-        return a.view(np.uint64) == POISON_F64_BITS
-    if a.dtype == np.uint64:
-        return a == POISON_F64_BITS
-    return a == POISON_I32
-
-
 # ---- the harness's files ---------------------------------------------------------------------------------------------------------------------
 def pack_case(op, B, ipar, dpar, arrays):
-    out = [MAGIC_IN, struct.pack("<5q", op, B, len(ipar), len(dpar), len(arrays)), struct.pack("<%dq" % len(ipar), *[int(v) for v in ipar]),
-           struct.pack("<%dd" % len(dpar), *[float(v) for v in dpar])]
-    for t, a in arrays:
-        a = np.zeros(0, _DT[t]) if a is None else np.ascontiguousarray(a, dtype=_DT[t]).reshape(-1)
-        out += [struct.pack("<2q", t, a.size), a.tobytes()]
-    return b"".join(out)
+    return IO.pack_case(MAGIC_IN, op, B, ipar, dpar, arrays)
 
 
 def unpack_case(buf):
-    assert buf[:8] == MAGIC_IN
-    op, B, nI, nD, nA = struct.unpack_from("<5q", buf, 8)
-    off = 48
-    ipar = list(struct.unpack_from("<%dq" % nI, buf, off)); off += 8 * nI
-    dpar = list(struct.unpack_from("<%dd" % nD, buf, off)); off += 8 * nD
-    arrays = []
-    for _ in range(nA):
-        t, n = struct.unpack_from("<2q", buf, off); off += 16
-        a = np.frombuffer(buf, dtype=_DT[t], count=n, offset=off).copy(); off += a.nbytes
-        arrays.append((t, a))
-    assert off == len(buf)
-    return op, B, ipar, dpar, arrays
+    return IO.unpack_case(MAGIC_IN, buf)
 
 
 def pack_result(form, arrays):
-    out = [MAGIC_OUT, struct.pack("<3q", form, GUARD, len(arrays))]
-    for t, a in arrays:
-        a = np.ascontiguousarray(a, dtype=_DT[t]).reshape(-1)
-        out += [struct.pack("<2q", t, a.size), a.tobytes()]
-    return b"".join(out)
+    return IO.pack_result(MAGIC_OUT, form, arrays)
 
 
 def unpack_result(buf):
     """-> (form = (Cholesky kernel, its G, Lanczos workgroups per matrix), [arrays as written, guard entries included])"""
-    assert buf[:8] == MAGIC_OUT, buf[:8]
-    form, guard, nA = struct.unpack_from("<3q", buf, 8)
-    assert guard == GUARD
-    off, arrays = 32, []
-    for _ in range(nA):
-        t, n = struct.unpack_from("<2q", buf, off); off += 16
-        a = np.frombuffer(buf, dtype=_DT[t], count=n, offset=off).copy(); off += a.nbytes
-        arrays.append(a)
-    assert off == len(buf), (off, len(buf))
+    form, arrays = IO.unpack_result(MAGIC_OUT, buf)
     return (form & 255, (form >> 8) & 255, (form >> 16) & 255), arrays
 
 

@@ -7,13 +7,10 @@ arrays in the harness's layout, whoever produced them (device = True: the harnes
 import struct
 from fractions import Fraction
 import numpy as np
+from tests.helpers.harness_io import GUARD, LD, U, bits, is_poison      # (re-exported: the tests read them under this module's name)
 
-LD = np.longdouble
-U = 2.0 ** -53
 OP_PRIMS, OP_STEP, OP_REWARD = 0, 1, 2
 MAGIC_IN, MAGIC_OUT = b"DYNCASE1", b"DYNRES01"
-GUARD = 64
-POISON_F64_BITS = np.frombuffer(b"\xa5" * 8, dtype=np.uint64)[0]
 PRIM_IN, PRIM_OUT, STEP_IN, STEP_OUT, REW_IN, REW_OUT = 14, 16, 14, 12, 5, 12
 OUT_WIDTH = {OP_PRIMS: PRIM_OUT, OP_STEP: STEP_OUT, OP_REWARD: REW_OUT}
 REGIMES = ("driving", "crawling", "stopped", "backwards", "spinning")
@@ -23,14 +20,6 @@ TINY_ANGLE = 1.0 / 32.0
 # columns of the primitives' input and output (tools/kbench_dynamics.hip)
 X, Q, ANG, CV, CLO, CHI, SV, STHR, FA, FB, FC, MUFZ, CA, FXT = range(14)
 O_RCP1, O_RCP, O_SQRT, O_RSQ_S, O_RSQ_R, O_SIN, O_COS, O_CSYM, O_CU, O_CVV, O_FMA, O_FYMAX, O_THR, O_K2, O_K3, O_SPARE = range(16)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def is_poison(a):
-    return bits(a) == POISON_F64_BITS
 
 
 # ================================================================ moved from tests/test_dynamics_shim.py ======================================

@@ -19,17 +19,15 @@ angle that is off by d = sigma_psi RNG_TOL + u |dpsi|, then two products and a s
 import os, struct
 import numpy as np
 from mpopis_amd.engine import plan_order
+from tests.helpers import harness_io as IO
+from tests.helpers.harness_io import DT, GUARD, LD, U, bits, is_poison, poisoned, ulp_of, ulp_err      # (re-exported: the tests read them under this module's name)
 
-LD = np.longdouble
-U = 2.0 ** -53
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 MAGIC_IN, MAGIC_OUT = b"LOPCASE1", b"LOPRES01"
-GUARD = 64
 OP_STEP, OP_LOOP, OP_PLAN, OP_REORDER = 0, 1, 2, 3
 ENV_MC, ENV_CAR, ENV_CP = 0, 1, 2
 KIND_NAME = {ENV_MC: "mountaincar", ENV_CAR: "car", ENV_CP: "cartpole"}
 ERR_NOT_PD, ERR_ACTION, ERR_HIP, ERR_NUMERIC = -2, -3, -4, -5
-DT = {0: np.float64, 1: np.int32, 2: np.uint64}
 RNG_TOL = 1e-13                                                              # tests/helpers/sample_cases.py: device normal against the libm normal
 ATAN2_ULP = 2                                                                # OCML's documented bound for the FP64 atan2
 NOISE_STREAM = 0x40000000                                                    # k_harness_update: philox_normal_pair(seed, step, 0x40000000, 0 / 1)
@@ -41,30 +39,6 @@ LOOP_OUT = (("hs_log", 0), ("alive_log", 1), ("x_log", 0), ("reward_log", 0), ("
             ("actlog", 0), ("status", 1), ("t", 1), ("states", 0), ("rewards", 0), ("iters", 1), ("tr_within", 1), ("tr_dist", 0), ("tr_beta", 0))
 PLAN_OUT = (("idx", 1), ("wsel", 0), ("controls", 0), ("Eplan", 0))
 TR_STATES, TR_REWARDS, TR_ITERS, TR_WITHIN, TR_DIST, TR_BETA = 1, 2, 4, 8, 16, 32
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def is_poison(a):
-    a = np.ascontiguousarray(a)
-    return (a.view(np.uint8).reshape(a.shape + (a.dtype.itemsize,)) == 0xA5).all(axis=-1)
-
-
-def poisoned(shape, t=0):
-    return np.frombuffer(b"\xa5" * (int(np.prod(shape)) * np.dtype(DT[t]).itemsize), dtype=DT[t]).copy().reshape(shape)
-
-
-def ulp_of(a):
-    a = np.abs(np.asarray(a, dtype=np.float64))
-    return np.maximum(np.spacing(a), 2.0 ** -1074)
-
-
-def ulp_err(got, ref_ld):
-    """|got - ref| in ulps of the float64 nearest the long-double reference"""
-    r64 = np.asarray(ref_ld, dtype=LD).astype(np.float64)
-    return (np.abs(np.asarray(got, dtype=np.float64).astype(LD) - np.asarray(ref_ld, dtype=LD)) / ulp_of(r64).astype(LD)).astype(np.float64)
 
 
 def gamma(k):
@@ -138,20 +112,12 @@ def _fields(L):
     return [L["J"], L["per"], L["elem"]], [], [(1 if L["elem"] == 4 else 0, L["in"])]
 
 
-def _arr(t, a):
-    if a is None:
-        return struct.pack("<2q", t, 0)
-    a = np.ascontiguousarray(a, dtype=DT[t])
-    return struct.pack("<2q", t, a.size) + a.tobytes()
-
-
 def pack(launches):
-    out = [MAGIC_IN, struct.pack("<q", len(launches))]
+    records = []
     for L in launches:
         ip, dp, arrays = _fields(L)
-        out += [struct.pack("<5q", L["op"], L["B"], len(ip), len(dp), len(arrays)), struct.pack("<%dq" % len(ip), *ip), struct.pack("<%dd" % len(dp), *dp)]
-        out += [_arr(t, a) for t, a in arrays]
-    return b"".join(out)
+        records.append(IO.pack_launch(L["op"], L["B"], ip, dp, arrays))
+    return IO.pack_launches(MAGIC_IN, records)
 
 
 def pack_result(launches, results, guard_hit=None):
@@ -162,13 +128,13 @@ def pack_result(launches, results, guard_hit=None):
         out.append(struct.pack("<2q", L["op"], len(names)))
         for n, t in names:
             if R.get(n) is None:
-                out.append(struct.pack("<2q", t, 0))
+                out.append(IO.pack_array(t, None))
                 continue
             g = poisoned((GUARD,), t)
             if guard_hit and guard_hit[:2] == (li, n):
                 g[guard_hit[2]] = 0
             a = np.ascontiguousarray(R[n], dtype=DT[t]).reshape(-1)
-            out.append(struct.pack("<2q", t, a.size + GUARD) + a.tobytes() + g.tobytes())
+            out.append(IO.pack_array(t, np.concatenate([a, g])))
     return b"".join(out)
 
 

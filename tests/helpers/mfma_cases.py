@@ -9,18 +9,14 @@ Nothing here touches the engine.  References are np.longdouble evaluations of th
            Weights from costs: + 4 u in the constant (relative error of exp).  A mean that had a shift added back carries one more rounding of
            the sum, u |ref| (half an ulp of the float64 result, which no kernel can avoid).
   A structural error -- a dropped column, a wrong row, a stale partial -- moves an entry by >= T / m; the bound is <= 2e-12 T at m = 4096."""
-import struct
 import numpy as np
+from tests.helpers import harness_io as IO
+from tests.helpers.harness_io import F64, I32, U64, GUARD, LD, U, bits, is_poison, split_guard           # (re-exported: the tests read them as M.<name>)
 
 OP_TRMM, OP_FUSED, OP_TWOKERNEL, OP_WCOV, OP_SHRINK, OP_CE_SMALL, OP_CE_GENERAL, OP_GATHER = range(8)
 MAGIC_IN, MAGIC_OUT = b"MFMCASE1", b"MFMRES01"
-GUARD = 64
-F64, I32, U64 = 0, 1, 2
-_DT = {F64: np.float64, I32: np.int32, U64: np.uint64}
 POISON_I32 = np.frombuffer(b"\xa5" * 4, dtype=np.int32)[0]
 POISON_F64_BITS = np.frombuffer(b"\xa5" * 8, dtype=np.uint64)[0]
-U = 2.0 ** -53
-LD = np.longdouble
 RNG_TOL = 1e-13                                            # tests/test_gpu_parity.py::test_device_rng_normals_full_size
 # enums of mpopis_amd/csrc/engine.h / include/mpopis.h
 WCOV_PAIR64, WCOV_PAIR16, WCOV_ROWS, WCOV_TALL = 0, 1, 2, 3
@@ -85,68 +81,21 @@ def scatter_cases():
 # ---- the harness's files ---------------------------------------------------------------------------------------------------------------
 def pack_case(op, B, ipar, dpar, arrays):
     """arrays: list of (type, array or None) in the op's fixed order (None = not given)"""
-    out = [MAGIC_IN, struct.pack("<5q", op, B, len(ipar), len(dpar), len(arrays)), struct.pack("<%dq" % len(ipar), *[int(v) for v in ipar]),
-           struct.pack("<%dd" % len(dpar), *[float(v) for v in dpar])]
-    for t, a in arrays:
-        a = np.zeros(0, _DT[t]) if a is None else np.ascontiguousarray(a, dtype=_DT[t]).reshape(-1)
-        out += [struct.pack("<2q", t, a.size), a.tobytes()]
-    return b"".join(out)
+    return IO.pack_case(MAGIC_IN, op, B, ipar, dpar, arrays)
 
 
 def unpack_case(buf):
-    assert buf[:8] == MAGIC_IN
-    op, B, nI, nD, nA = struct.unpack_from("<5q", buf, 8)
-    off = 48
-    ipar = list(struct.unpack_from("<%dq" % nI, buf, off)); off += 8 * nI
-    dpar = list(struct.unpack_from("<%dd" % nD, buf, off)); off += 8 * nD
-    arrays = []
-    for _ in range(nA):
-        t, n = struct.unpack_from("<2q", buf, off); off += 16
-        a = np.frombuffer(buf, dtype=_DT[t], count=n, offset=off).copy(); off += a.nbytes
-        arrays.append((t, a))
-    assert off == len(buf)
-    return op, B, ipar, dpar, arrays
+    return IO.unpack_case(MAGIC_IN, buf)
 
 
 def pack_result(form, arrays):
     """what the harness writes (used by the CPU round-trip test); arrays: list of (type, array with its guard entries)"""
-    out = [MAGIC_OUT, struct.pack("<3q", form, GUARD, len(arrays))]
-    for t, a in arrays:
-        a = np.ascontiguousarray(a, dtype=_DT[t]).reshape(-1)
-        out += [struct.pack("<2q", t, a.size), a.tobytes()]
-    return b"".join(out)
+    return IO.pack_result(MAGIC_OUT, form, arrays)
 
 
 def unpack_result(buf):
     """-> (form, [arrays as written, guard entries included])"""
-    assert buf[:8] == MAGIC_OUT, buf[:8]
-    form, guard, nA = struct.unpack_from("<3q", buf, 8)
-    assert guard == GUARD
-    off, arrays = 32, []
-    for _ in range(nA):
-        t, n = struct.unpack_from("<2q", buf, off); off += 16
-        a = np.frombuffer(buf, dtype=_DT[t], count=n, offset=off).copy(); off += a.nbytes
-        arrays.append(a)
-    assert off == len(buf), (off, len(buf))
-    return form, arrays
-
-
-def is_poison(a):
-    a = np.asarray(a)
-    if a.dtype == np.float64:
-        return a.view(np.uint64) == POISON_F64_BITS
-    return a == POISON_I32
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def split_guard(a, shape):
-    """-> (body reshaped, guard)"""
-    n = int(np.prod(shape))
-    assert a.size == n + GUARD, (a.size, n)
-    return a[:n].reshape(shape), a[n:]
+    return IO.unpack_result(MAGIC_OUT, buf)
 
 
 def actives(B, inactive):

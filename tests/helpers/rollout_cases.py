@@ -10,39 +10,24 @@ import os
 import re
 import struct
 import numpy as np
+from tests.helpers import harness_io as IO
+from tests.helpers.harness_io import DT, GUARD, LD, U, bits, is_poison, poisoned      # (re-exported: the tests read them under this module's name)
 
-LD = np.longdouble
-U = 2.0 ** -53
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CSRC = os.path.join(ROOT, "mpopis_amd", "csrc")
 MAGIC_IN, MAGIC_OUT = b"ROLCASE1", b"ROLRES01"
-GUARD = 64
 OP_ROLLOUT, OP_BEGIN = 0, 1
 ENV_MC, ENV_CAR, ENV_CP = 0, 1, 2
 SIMPLE2, SIMPLE4, CUSTOM, TWO_WAVE, SPB1, SPB4 = range(6)                   # engine.h: RolloutBody
 BODY_NAME = {SIMPLE2: "simple-2", SIMPLE4: "simple-4", CUSTOM: "custom", TWO_WAVE: "two-wave", SPB1: "one-wave SPB 1", SPB4: "one-wave SPB 4"}
 ERR_ACTION = -3
 RTOL = 1e-8                                                                  # tests/test_gpu_parity.py, with its 1e-9 floor
-DT = {0: np.float64, 1: np.int32, 2: np.uint64}
 POISON64 = np.uint64(0xA5A5A5A5A5A5A5A5)
 ALL_ONES = np.uint64(0xFFFFFFFFFFFFFFFF)
 DUO_ALWAYS = 1 << 30                                                         # MPOPIS_ROLLOUT_DUO: every launch without the logger takes the two-wave body
 ROLLOUT_OUT = ("cost", "traj", "cmin", "status", "iters", "xext")
 BEGIN_OUT = ("status", "active", "iters", "iters_acc", "Uin", "Ucur", "cmin", "xext", "xref")
 OUT_TYPE = dict(cost=0, traj=0, cmin=2, status=1, iters=1, xext=0, active=1, iters_acc=2, Uin=0, Ucur=0, xref=0)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def is_poison(a):
-    a = np.ascontiguousarray(a)
-    return (a.view(np.uint8).reshape(a.shape + (a.dtype.itemsize,)) == 0xA5).all(axis=-1)
-
-
-def poisoned(shape, t=0):
-    return np.frombuffer(b"\xa5" * (int(np.prod(shape)) * np.dtype(DT[t]).itemsize), dtype=DT[t]).copy().reshape(shape)
 
 
 def cost_key(v):
@@ -117,19 +102,12 @@ def _fields(L):
     return ip, arrays
 
 
-def _arr(t, a):
-    if a is None:
-        return struct.pack("<2q", t, 0)
-    a = np.ascontiguousarray(a, dtype=DT[t])
-    return struct.pack("<2q", t, a.size) + a.tobytes()
-
-
 def pack(launches):
-    out = [MAGIC_IN, struct.pack("<q", len(launches))]
+    records = []
     for L in launches:
         ip, arrays = _fields(L)
-        out += [struct.pack("<5q", L["op"], L["B"], len(ip), 0, len(arrays)), struct.pack("<%dq" % len(ip), *ip)] + [_arr(t, a) for t, a in arrays]
-    return b"".join(out)
+        records.append(IO.pack_launch(L["op"], L["B"], ip, [], arrays))
+    return IO.pack_launches(MAGIC_IN, records)
 
 
 def state_size(L):
@@ -159,14 +137,14 @@ def pack_result(launches, results):
         for n in names:
             shape, t = out_shapes(L)[n], OUT_TYPE[n]
             if shape is None:
-                out.append(struct.pack("<2q", t, 0))
+                out.append(IO.pack_array(t, None))
                 continue
             g = poisoned((GUARD,), t)
             if R.get("guard") and R["guard"][0] == n:
                 g[R["guard"][1]] = R["guard"][2]
             a = np.ascontiguousarray(R[n], dtype=DT[t]).reshape(-1)
             assert a.size == int(np.prod(shape)), (n, a.size, shape)
-            out.append(struct.pack("<2q", t, a.size + GUARD) + a.tobytes() + g.tobytes())
+            out.append(IO.pack_array(t, np.concatenate([a, g])))
     return b"".join(out)
 
 

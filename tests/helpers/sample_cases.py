@@ -19,10 +19,10 @@ import re
 import struct
 from fractions import Fraction
 import numpy as np
+from tests.helpers.harness_io import GUARD, LD, U, bits, is_poison, ulp_of      # (re-exported: the tests read them under this module's name)
 
 OP_TAB, OP_WORDS, OP_BOXMULLER, OP_NORMALQ, OP_NORMALS, OP_DRAWS, OP_FINALIZE, OP_T_IN, OP_T_OUT = range(9)
 MAGIC_IN, MAGIC_OUT = b"SMPCASE1", b"SMPRES01"
-GUARD = 64
 MAX_AS = 16                                                # kMaxAs of engine.h
 POISON_I32 = np.frombuffer(b"\xa5" * 4, dtype=np.int32)[0]
 POISON_U32 = np.frombuffer(b"\xa5" * 4, dtype=np.uint32)[0]
@@ -30,8 +30,6 @@ POISON_F64_BITS = np.frombuffer(b"\xa5" * 8, dtype=np.uint64)[0]
 SINGLE, PAIR, QUAD = 0, 1, 2                               # enum SampleNormalForm of engine.h
 RNG_TOL = 1e-13                                            # tests/test_gpu_parity.py::test_device_rng_normals_full_size: the outer contract
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-LD = np.longdouble
-U = 2.0 ** -53
 
 
 def table_sizes():
@@ -150,19 +148,6 @@ def unpack_result(buf, op, **shape):
     return r
 
 
-def is_poison(a):
-    a = np.asarray(a)
-    if a.dtype == np.float64:
-        return a.view(np.uint64) == POISON_F64_BITS
-    if a.dtype == np.uint32:
-        return a == POISON_U32
-    return a == POISON_I32
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
 # ---- Philox4x32-10 ------------------------------------------------------------------------------------------------------------------------
 KAT = [  # Random123 kat_vectors, philox4x32-10 (tests/test_oracle_kat.py): counter, key, output
     ([0, 0, 0, 0], [0, 0], [0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8]),
@@ -238,10 +223,6 @@ def _sin_pi_over(n, d):
 def table_f64():
     """table_ref rounded to double: the table a correctly rounding host would make (the CPU restatement's table)"""
     return table_ref().astype(np.float64)
-
-
-def ulp_of(x):
-    return np.spacing(np.abs(np.asarray(x, dtype=np.float64)))
 
 
 # ---- Box-Muller: directed words -------------------------------------------------------------------------------------------------------------

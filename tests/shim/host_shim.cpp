@@ -5,15 +5,6 @@
 #include <vector>
 #include <cstring>
 using namespace mpopis;
-#include <algorithm>
-static std::vector<double> g_nd, g_ring, g_cert; static std::vector<int> g_ni;
-static Track mk(int P, const double* tx, const double* ty, const double* tw, std::vector<double>& n2) {
-    n2.resize(P); for (int i = 0; i < P; ++i) n2[i] = tx[i] * tx[i] + ty[i] * ty[i];
-    const int W = std::min<int>(kTrackNbrW, P);
-    build_track_tables(P, tx, ty, g_nd, g_ni);
-    build_track_ring(P, tx, ty, tw, n2.data(), g_nd, g_ring, g_cert);
-    return Track{tx, ty, tw, n2.data(), P, g_ni.data(), g_nd.data(), W, g_ring.data(), g_cert.data()};
-}
 extern "C" {
 void shim_car_action_step(const double* p20, double* s8, double a0, double a1) {
     CarParams p = make_car_params(p20);
@@ -23,14 +14,14 @@ void shim_car_action_step(const double* p20, double* s8, double a0, double a1) {
 }
 double shim_car_reward(const double* p20, int P, const double* tx, const double* ty, const double* tw, const double* s8) {
     CarParams p = make_car_params(p20);
-    std::vector<double> n2; Track tk = mk(P, tx, ty, tw, n2);
+    const TrackHost th(P, tx, ty, tw); const Track tk = th.view();
     return car_reward(p, tk, s8[0], s8[1], s8[3], s8[4]);
 }
 // full single-car rollout: controls as x T (already clamped); returns -sum(reward)
 double shim_car_rollout(const double* p20, int P, const double* tx, const double* ty, const double* tw,
                         double* s8, const double* ctrl, int T) {
     CarParams p = make_car_params(p20);
-    std::vector<double> n2; Track tk = mk(P, tx, ty, tw, n2);
+    const TrackHost th(P, tx, ty, tw); const Track tk = th.view();
     double c = 0.0;
     CarState st; car_state_from8(st, s8);          // sin/cos evaluated once, then carried (as in the kernel)
     for (int t = 0; t < T; ++t) { car_action_step(p, st, ctrl[2 * t], ctrl[2 * t + 1]); c -= car_reward(p, tk, st.x, st.y, st.Vx, st.Vy, &st.near); }
@@ -41,14 +32,14 @@ void shim_mc_step(const double* p8, double* s2, int* t, int* done, double f) { M
 double shim_mc_reward(const double* p8, const double* s2, int done) { McParams p = make_mc_params(p8); return mc_reward(p, s2, done); }
 }
 extern "C" int shim_within_anchor(int P, const double* tx, const double* ty, const double* tw, double px, double py, int* anchor, double* dist) {
-    static std::vector<double> n2; static Track tk; static const double* last = nullptr;
-    if (last != tx) { tk = mk(P, tx, ty, tw, n2); last = tx; }
+    static TrackHost th; static Track tk; static const double* last = nullptr;
+    if (last != tx) { th = TrackHost(P, tx, ty, tw); tk = th.view(); last = tx; }
     return within_track(tk, px, py, dist, anchor) ? 1 : 0;
 }
 // the rollout kernels' path: ring fast path when it applies, general search otherwise (car_dynamics.h: car_reward); *fast = which one ran
 extern "C" int shim_within_ring(int P, const double* tx, const double* ty, const double* tw, double px, double py, int* anchor, double* dist, int* fast) {
-    static std::vector<double> n2; static Track tk; static const double* last = nullptr;
-    if (last != tx) { tk = mk(P, tx, ty, tw, n2); last = tx; }
+    static TrackHost th; static Track tk; static const double* last = nullptr;
+    if (last != tx) { th = TrackHost(P, tx, ty, tw); tk = th.view(); last = tx; }
     int rel = 0;
     bool ok = ring_candidates(tk.ring, tk.ring_cert, *anchor, px, py, -2.0 * px, -2.0 * py, &rel);
     *fast = ok ? 1 : 0;
@@ -92,7 +83,7 @@ extern "C" void shim_dyn_step(const double* p20, int psi, int renorm, const doub
 // reward, the two ring masks (bit 0 = the single caller) with rel, and the unanchored search; in[n][5] = { px, py, Vx, Vy, anchor }
 extern "C" void shim_dyn_reward(const double* p20, int P, const double* tx, const double* ty, const double* tw, int n, const double* in, double* out) {
     const CarParams p = make_car_params(p20);
-    std::vector<double> n2; Track tk = mk(P, tx, ty, tw, n2);
+    const TrackHost th(P, tx, ty, tw); const Track tk = th.view();
     for (int i = 0; i < n; ++i) {
         const double* a = in + (size_t)i * 5; double* o = out + (size_t)i * 12;
         const double px = a[0], py = a[1], m2x = -2.0 * px, m2y = -2.0 * py;
@@ -114,7 +105,7 @@ extern "C" void shim_dyn_reward(const double* p20, int P, const double* tx, cons
 extern "C" void shim_car_rollout_log(const double* p20, int P, const double* tx, const double* ty, const double* tw, int n, const double* s8, const double* ctrl, int T,
                                      double* states, double* rew, int* near) {
     const CarParams p = make_car_params(p20);
-    std::vector<double> n2; Track tk = mk(P, tx, ty, tw, n2);
+    const TrackHost th(P, tx, ty, tw); const Track tk = th.view();
     for (int i = 0; i < n; ++i) {
         CarState st; car_state_from8(st, s8 + (size_t)i * 8);
         double dist; int a = -1;

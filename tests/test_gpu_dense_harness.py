@@ -12,9 +12,10 @@ references are what they claim), never the engine; every stage of a chain is che
 MPOPIS_COOP_MAX_WG=64 pins the form selection (never above the device's CU count).
 
 Every check prints `RATIO <op> <output> <worst error / bound>`; DESIGN.md ("kernel-level tests") records the worst per op and output."""
-import os, shutil, subprocess
+import os
 import numpy as np
 import pytest
+from tests.helpers import harness_run as HR
 from tests.helpers import dense_cases as D
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,32 +26,14 @@ KNOBS = ("MPOPIS_POTRF_REG", "MPOPIS_POTRF_G", "MPOPIS_POTRF_S", "MPOPIS_LANCZOS
 
 @pytest.fixture(scope="module")
 def harness():
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available to build the harness")
-    from mpopis_amd import build
-    build.build()                                                     # the harness links the library's object files
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_dense.sh")], capture_output=True, text=True, timeout=600)
-    exe = os.path.join(ROOT, "tools", "kbench_dense_bin")
-    assert out.returncode == 0 and os.path.exists(exe), out.stdout + out.stderr
-    return exe
+    return HR.build("dense")
 
 
 def _run(exe, tmp_path, data, env=None):
-    fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "result.bin")
-    with open(fin, "wb") as f:
-        f.write(data)
-    if os.path.exists(fout):
-        os.remove(fout)
     e = {k: v for k, v in os.environ.items() if k not in KNOBS}
     e["MPOPIS_COOP_MAX_WG"] = str(D.MAX_WG)
     e.update(env or {})
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120, env=e)
-    if r.returncode < 0 or r.returncode in (134, 139) or "HIP error" in r.stdout:
-        # a fault, an abort or a crash of the harness: nothing more is started on this GPU -- the session ends here with what the process left
-        pytest.exit("tools/kbench_dense_bin died (%s): %s" % (r.returncode, (r.stdout + r.stderr)[-2000:]), returncode=3)
-    assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
-    with open(fout, "rb") as f:
-        return D.unpack_result(f.read())
+    return D.unpack_result(HR.run_case(exe, tmp_path, data, env=e))
 
 
 def _body(a, shape, computed, name, keep=None):

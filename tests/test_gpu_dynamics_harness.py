@@ -25,9 +25,10 @@ Measured on the MI355X (every run prints its own): fast_rcp1 10.23 ulp, fast_rcp
 0.70 (cos) ulp; tire_consts 0.99 / 3.29 / 3.62 / 5.74 u; model step 1.4e-15 driving, 2.1e-14 crawling, 2.1e-12 stopped, 1.6e-15 backwards, 2.1e-15 spinning in
 all four forms, none set aside, 1.9e-13 under random parameters; distance 1.60 (default track) / 1.52 (3-point ring) / 1.98 (5-point ring) u |p - p1|; reward
 1.4e-14 from the oracle's."""
-import os, shutil, subprocess
+import os
 import numpy as np
 import pytest
+from tests.helpers import harness_run as HR
 from tests.helpers import dynamics_cases as D
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,24 +38,11 @@ TRACKS = {n: t for n, t in D.tracks() if n in ("curve", "ring3", "ring5")}
 
 @pytest.fixture(scope="module")
 def harness():
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available to build the harness")
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_dynamics.sh")], capture_output=True, text=True, timeout=600)      # header-only: nothing of the library
-    exe = os.path.join(ROOT, "tools", "kbench_dynamics_bin")
-    assert out.returncode == 0 and os.path.exists(exe), out.stdout + out.stderr
-    return exe
+    return HR.build("dynamics", library=False)      # header-only: nothing of the library
 
 
 def _run(exe, tmp_path, case, op, ns):
-    fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "result.bin")
-    with open(fin, "wb") as f:
-        f.write(case)
-    if os.path.exists(fout):
-        os.remove(fout)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
-    with open(fout, "rb") as f:
-        return D.unpack_result(f.read(), op, ns)                         # checks the header (which operation ran, how many launches) and every guard
+    return D.unpack_result(HR.run_case(exe, tmp_path, case), op, ns)     # checks the header (which operation ran, how many launches) and every guard
 
 
 # ================================================================ 1. primitives ================================================================

@@ -1,8 +1,9 @@
 """The dense linear algebra kernels (Cholesky: LDS / register-resident / cooperative / one-workgroup global; triangular-inverse trace; Lanczos inverse square root:
 one workgroup / cooperative) exercised directly, below the policy level, through the C++ harness tools/kbench_linalg.hip: sizes on both sides of
 every kernel-selection threshold, batches that do and do not allow co-resident clusters."""
-import os, re, shutil, subprocess
+import os, re, shutil
 import pytest
+from tests.helpers import harness_run as HR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -14,7 +15,7 @@ def harness():
         pytest.skip("hipcc not available to build the harness")
     from mpopis_amd import build
     build.build()                                                     # the harness links the library's object files
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_linalg.sh")], capture_output=True, text=True, timeout=600)
+    out = HR.run(["bash", os.path.join(ROOT, "tools", "build_kbench_linalg.sh")], timeout=600)
     exe = os.path.join(ROOT, "tools", "kbench_linalg_bin")
     assert os.path.exists(exe), out.stdout + out.stderr
     return exe
@@ -45,7 +46,7 @@ def test_register_cholesky_has_the_bits_of_the_other_kernels(harness, B, n):
     first and then the subtraction): the factors are bit-identical, zeros above the diagonal included (the harness poisons the output first)"""
     hashes = []
     for env in ({}, {"MPOPIS_POTRF_REG": "0"}, {"MPOPIS_POTRF_REG": "0", "MPOPIS_POTRF_G": "0"}):
-        r = subprocess.run([harness, str(B), str(n)], capture_output=True, text=True, timeout=120, env=dict(os.environ, KB_POTRF_ONLY="1", **env))
+        r = HR.run([harness, str(B), str(n)], env=dict(os.environ, KB_POTRF_ONLY="1", **env))
         assert r.returncode == 0, r.stdout + r.stderr
         assert _num(r"potrf status min (-?\d+)", r.stdout) == 0 and _num(r"max \|upper\| = ([0-9.e+-]+)", r.stdout) == 0.0
         m = re.search(r"potrf L hash ([0-9a-f]+)", r.stdout)
@@ -55,7 +56,7 @@ def test_register_cholesky_has_the_bits_of_the_other_kernels(harness, B, n):
 
 
 def _check(harness, B, n, env):
-    r = subprocess.run([harness, str(B), str(n)], capture_output=True, text=True, timeout=120, env=dict(os.environ, **env))
+    r = HR.run([harness, str(B), str(n)], env=dict(os.environ, **env))
     assert r.returncode == 0, r.stdout + r.stderr
     t = r.stdout
     assert _num(r"potrf status min (-?\d+)", t) == 0
@@ -75,7 +76,7 @@ def test_dense_fallback_beyond_the_quadrature(harness, B, n, decades):
     hands the slot to the one-workgroup Jacobi eigen-solve (dense_invsqrt_slot) instead of reporting MPOPIS_ERR_NUMERIC -- the reference's eigen-based
     Σ^-0.5 (:580) has no conditioning limit.  Checked by identities that stay well-posed at this conditioning: y'y = b'A^-1 b (host forward substitution
     with the Cholesky factor, long double), y'A y = b'b, and tr(A^-1) against the triangular inverse's."""
-    r = subprocess.run([harness, str(B), str(n)], capture_output=True, text=True, timeout=300, env=dict(os.environ, KB_GRADE=str(decades)))
+    r = HR.run([harness, str(B), str(n)], timeout=300, env=dict(os.environ, KB_GRADE=str(decades)))
     assert r.returncode == 0, r.stdout + r.stderr
     t = r.stdout
     assert _num(r"potrf status min (-?\d+)", t) == 0

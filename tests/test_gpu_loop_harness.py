@@ -50,9 +50,10 @@ Not asserted: an exact pair distance of 4.0 from a 3-4-5 offset does not exist i
 through a step), the 3-4-5 offset gives 5.0 exactly.  The state of a simple env after an out-of-range action is not compared (the oracle refuses the step).
 
 Found: nothing wrong in the kernels.  Measured on the MI355X (every run prints its own; DESIGN.md section 2 has the same): see MEASURED below."""
-import os, shutil, subprocess
+import os
 import numpy as np
 import pytest
+from tests.helpers import harness_run as HR
 from tests.helpers import loop_cases as LC
 
 MEASURED = """vmean error / bound 0.21 (1 car), 0.20 (3), 0.09 (8), 0.28 (per-slot envs), 0.31 (6 steps after the noise); bmean error / bound 0.21, 0.19, 0.19, 0.21, 0.17
@@ -67,32 +68,11 @@ NS = 54
 
 @pytest.fixture(scope="module")
 def harness():
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available to build the harness")
-    from mpopis_amd import build
-    build.build()                                                     # the harness links the library's object files
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_loop.sh")], capture_output=True, text=True, timeout=600)
-    exe = os.path.join(ROOT, "tools", "kbench_loop_bin")
-    assert out.returncode == 0 and os.path.exists(exe), out.stdout + out.stderr
-    return exe
+    return HR.build("loop")
 
 
 def _run(exe, tmp_path, launches):
-    fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "result.bin")
-    with open(fin, "wb") as f:
-        f.write(LC.pack(launches))
-    if os.path.exists(fout):
-        os.remove(fout)
-    try:
-        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-    except subprocess.TimeoutExpired as t:
-        pytest.exit("tools/kbench_loop_bin hung: %s" % str(t.stdout)[-2000:], returncode=3)      # a hang: nothing more is started on this GPU either
-    if r.returncode < 0 or r.returncode in (134, 139) or "HIP error" in r.stdout:
-        # a fault, an abort or a crash of the harness: nothing more is started on this GPU -- the session ends here with what the process left
-        pytest.exit("tools/kbench_loop_bin died (%s): %s" % (r.returncode, (r.stdout + r.stderr)[-2000:]), returncode=3)
-    assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
-    with open(fout, "rb") as f:
-        return LC.unpack_result(f.read(), launches)                       # checks every guard
+    return LC.unpack_result(HR.run_case(exe, tmp_path, LC.pack(launches)), launches)      # checks every guard
 
 
 def _alive0(B):

@@ -10,9 +10,10 @@ inactive slots and guard entries must stay untouched and no active entry may kee
 Every check prints `RATIO <op> <worst error / bound>`; DESIGN.md ("kernel-level tests") records the worst per op.
 A second run of the same case must give the same bits; that is asserted for every op of the harness and every form of the sampler and the scatter on
 chosen cases, not on all of them, to keep the run time of the file down."""
-import os, shutil, subprocess
+import os
 import numpy as np
 import pytest
+from tests.helpers import harness_run as HR
 from tests.helpers import mfma_cases as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,38 +21,16 @@ pytestmark = pytest.mark.gpu
 LD = M.LD
 
 
-def _build_harness():
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available to build the harness")
-    from mpopis_amd import build
-    build.build()                                                     # the harness links the library's object files
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_mfma.sh")], capture_output=True, text=True, timeout=600)
-    exe = os.path.join(ROOT, "tools", "kbench_mfma_bin")
-    assert out.returncode == 0 and os.path.exists(exe), out.stdout + out.stderr
-    return exe
-
-
 @pytest.fixture(scope="module")
 def harness():
-    return _build_harness()
+    return HR.build("mfma")
 
 
 def _run(exe, tmp_path, data, env=None):
-    fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "result.bin")
-    with open(fin, "wb") as f:
-        f.write(data)
-    if os.path.exists(fout):
-        os.remove(fout)
     e = dict(os.environ)
     e.pop("MPOPIS_WCOV_ROWS", None)
     e.update(env or {})
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120, env=e)
-    if r.returncode < 0 or r.returncode in (134, 139) or "HIP error" in r.stdout:
-        # a fault, an abort or a crash of the harness: nothing more is started on this GPU -- the session ends here with what the process left
-        pytest.exit("tools/kbench_mfma_bin died (%s): %s" % (r.returncode, (r.stdout + r.stderr)[-2000:]), returncode=3)
-    assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
-    with open(fout, "rb") as f:
-        return M.unpack_result(f.read())
+    return M.unpack_result(HR.run_case(exe, tmp_path, data, env=e))
 
 
 def _same(r1, r2):

@@ -30,9 +30,10 @@ Measured on the MI355X (every run prints its own; DESIGN.md, "Launch-level tests
 from the oracle, two-wave = SPB 1 / SPB 4: 1 car 1.9e-15 / 2.4e-15, 2 cars 1.1e-15 / 1.4e-15, 3 cars 3.0e-15 / 2.6e-15, 4 cars 5.5e-14 / 7.8e-15, 5 cars 2.4e-15 /
 3.6e-15, 6 cars 8.9e-16 / 1.3e-15, 7 cars 1.9e-16 / 3.7e-16, 8 cars 3.7e-16 / 3.7e-16; (c) RATIO LOGGER <= 0.0005, states <= 3.2e-15 per step, none set aside;
 (e) RATIO GAMMA 0.074 (1 car), 0.014 (4 cars); (f) MountainCar 5.5e-16, CartPole 6.8e-16."""
-import os, shutil, subprocess
+import os
 import numpy as np
 import pytest
+from tests.helpers import harness_run as HR
 from tests.helpers import rollout_cases as RC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,36 +43,15 @@ BODIES = (RC.TWO_WAVE, RC.SPB1, RC.SPB4)
 
 @pytest.fixture(scope="module")
 def harness():
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available to build the harness")
-    from mpopis_amd import build
-    build.build()                                                     # the harness links the library's object files
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_rollout.sh")], capture_output=True, text=True, timeout=600)
-    exe = os.path.join(ROOT, "tools", "kbench_rollout_bin")
-    assert out.returncode == 0 and os.path.exists(exe), out.stdout + out.stderr
-    return exe
+    return HR.build("rollout")
 
 
 def _run(exe, tmp_path, launches, env):
-    fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "result.bin")
-    with open(fin, "wb") as f:
-        f.write(RC.pack(launches))
-    if os.path.exists(fout):
-        os.remove(fout)
     e = dict(os.environ)
     for k in ("MPOPIS_ROLLOUT_DUO", "MPOPIS_COOP_MAX_WG"):
         e.pop(k, None)
     e.update(env)
-    try:
-        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120, env=e)
-    except subprocess.TimeoutExpired as t:
-        pytest.exit("tools/kbench_rollout_bin hung: %s" % str(t.stdout)[-2000:], returncode=3)      # a hang: nothing more is started on this GPU either
-    if r.returncode < 0 or r.returncode in (134, 139) or "HIP error" in r.stdout:
-        # a fault, an abort or a crash of the harness: nothing more is started on this GPU -- the session ends here with what the process left
-        pytest.exit("tools/kbench_rollout_bin died (%s): %s" % (r.returncode, (r.stdout + r.stderr)[-2000:]), returncode=3)
-    assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
-    with open(fout, "rb") as f:
-        res = RC.unpack_result(f.read(), launches)                       # checks every guard
+    res = RC.unpack_result(HR.run_case(exe, tmp_path, RC.pack(launches), env=e), launches)      # checks every guard
     for L, R in zip(launches, res):
         if L["op"] == RC.OP_ROLLOUT:
             RC.check_form(L, R, *RC.env_form_args(env))

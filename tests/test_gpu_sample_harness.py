@@ -5,9 +5,10 @@ Every NORMALS case asserts the form sample_normal_form reported, so a moved cond
 References are NumPy (np.longdouble where arithmetic is involved) and the oracle (tests/helpers/sample_cases.py; tests/test_sample_cases_cpu.py
 proves them and the derived Box-Muller bound on the CPU), never the engine.  The harness poisons every output first: inactive slots and the
 entries past the end must stay untouched, and no active entry may keep the poison."""
-import os, shutil, subprocess
+import os
 import numpy as np
 import pytest
+from tests.helpers import harness_run as HR
 from tests.helpers import sample_cases as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,35 +17,13 @@ B = 3
 NMAX = 8256                                                           # normals per (seed, stream) the placement reference holds: >= 32 x 257
 
 
-def _build_harness():
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available to build the harness")
-    from mpopis_amd import build
-    build.build()                                                     # the harness links the library's object files
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_sample.sh")], capture_output=True, text=True, timeout=600)
-    exe = os.path.join(ROOT, "tools", "kbench_sample_bin")
-    assert out.returncode == 0 and os.path.exists(exe), out.stdout + out.stderr
-    return exe
-
-
 @pytest.fixture(scope="module")
 def harness():
-    return _build_harness()
+    return HR.build("sample")
 
 
 def _run(exe, tmp_path, case, op, **shape):
-    fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "result.bin")
-    with open(fin, "wb") as f:
-        f.write(case)
-    if os.path.exists(fout):
-        os.remove(fout)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-    if r.returncode < 0 or r.returncode in (134, 139) or "HIP error" in r.stdout:
-        # a fault, an abort or a crash of the harness: nothing more is started on this GPU -- the session ends here with what the process left
-        pytest.exit("tools/kbench_sample_bin died (%s): %s" % (r.returncode, (r.stdout + r.stderr)[-2000:]), returncode=3)
-    assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
-    with open(fout, "rb") as f:
-        return S.unpack_result(f.read(), op, **shape)
+    return S.unpack_result(HR.run_case(exe, tmp_path, case), op, **shape)
 
 
 def _clean(r, name):

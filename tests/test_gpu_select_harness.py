@@ -8,41 +8,23 @@ untouched.
 
 Not asserted: the relative order of +0.0 and -0.0.  The device and the oracle compare numerically (equal keys, index decides) where Julia's isless
 puts -0.0 first; no input here holds a negative zero."""
-import os, shutil, subprocess
+import os
 import numpy as np
 import pytest
+from tests.helpers import harness_run as HR
 from tests.helpers import select_cases as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def _build_harness():
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available to build the harness")
-    from mpopis_amd import build
-    build.build()                                                     # the harness links the library's object files
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_select.sh")], capture_output=True, text=True, timeout=600)
-    exe = os.path.join(ROOT, "tools", "kbench_select_bin")
-    assert out.returncode == 0 and os.path.exists(exe), out.stdout + out.stderr
-    return exe
-
-
 @pytest.fixture(scope="module")
 def harness():
-    return _build_harness()
+    return HR.build("select")
 
 
 def _run(exe, tmp_path, case, op, B, K, env=None, log_stride=0):
-    fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "result.bin")
-    with open(fin, "wb") as f:
-        f.write(case)
-    if os.path.exists(fout):
-        os.remove(fout)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120, env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
-    with open(fout, "rb") as f:
-        return S.unpack_result(f.read(), op, B, K, log_stride=log_stride)
+    return S.unpack_result(HR.run_case(exe, tmp_path, case, env=dict(os.environ, **(env or {}))), op, B, K, log_stride=log_stride)
 
 
 def _bits(a):

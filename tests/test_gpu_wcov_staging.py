@@ -3,9 +3,10 @@ tile a staged element is one multiply by the column's sqrt(w_k) -- 0 for a colum
 elements are guarded (data row, the ones row, zero padding).  Driven through tools/kbench_mfma.hip like tests/test_gpu_mfma_harness.py, one process per
 launch; cases, references (np.longdouble) and the bound 4 (m + 64) u T_ab come from tests/helpers/mfma_cases.py, the case list from
 tests/helpers/wcov_staging_cases.py (tests/test_wcov_staging_cpu.py shows on the CPU what it reaches).  Every case asserts the form wcov_form reported."""
-import os, shutil, subprocess
+import os
 import numpy as np
 import pytest
+from tests.helpers import harness_run as HR
 from tests.helpers import mfma_cases as M
 from tests.helpers import wcov_staging_cases as W
 
@@ -17,32 +18,19 @@ SPECS = W.specs()
 
 @pytest.fixture(scope="module")
 def harness():
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available to build the harness")
     from mpopis_amd import build
     lib = build.build()                                               # the harness links the library's object files
-    exe, src = os.path.join(ROOT, "tools", "kbench_mfma_bin"), os.path.join(ROOT, "tools", "kbench_mfma.hip")
-    if not (os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(lib), os.path.getmtime(src))):
-        out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_kbench_mfma.sh")], capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and os.path.exists(exe), out.stdout + out.stderr
-    return exe
+    exe = os.path.join(ROOT, "tools", "kbench_mfma_bin")
+    deps = [lib] + [os.path.join(ROOT, "tools", f) for f in ("kbench_mfma.hip", "kbench_dev.h", "kbench_io.h", "build_kbench.sh")]
+    if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(d) for d in deps):
+        return exe                                                    # (tests/test_gpu_mfma_harness.py built it in this session)
+    return HR.build("mfma")
 
 
 def _run(exe, tmp_path, data):
-    fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "result.bin")
-    with open(fin, "wb") as f:
-        f.write(data)
-    if os.path.exists(fout):
-        os.remove(fout)
     e = dict(os.environ)
     e.pop("MPOPIS_WCOV_ROWS", None)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120, env=e)
-    if r.returncode < 0 or r.returncode in (134, 139) or "HIP error" in r.stdout:
-        # a fault, an abort or a crash of the harness: nothing more is started on this GPU
-        pytest.exit("tools/kbench_mfma_bin died (%s): %s" % (r.returncode, (r.stdout + r.stderr)[-2000:]), returncode=3)
-    assert r.returncode == 0, (r.returncode, r.stdout + r.stderr)
-    with open(fout, "rb") as f:
-        form, arrays = M.unpack_result(f.read())
+    form, arrays = M.unpack_result(HR.run_case(exe, tmp_path, data, env=e))
     assert len(arrays) == 5                                           # S, mu_out, u_add, cmin, part
     return form, arrays
 

@@ -2,7 +2,7 @@
 // v_min / v_max / v_fma forms, the wave masks of the ring tiers, exec) on the inputs of a case file, one lane per case, and writes the raw device
 // outputs back to a file (dev / test tool, not shipped).  It holds no reference arithmetic: tests/test_gpu_dynamics_harness.py writes the case, reads
 // the result and compares with long double, the oracle and NumPy.  Header-only: includes car_dynamics.h and links nothing of the library.
-// build: tools/build_kbench_dynamics.sh        run: tools/kbench_dynamics_bin <case file> <result file>
+// build: tools/build_kbench.sh dynamics       run: tools/kbench_dynamics_bin <case file> <result file>
 //
 // case file (little endian; layout shared with tests/helpers/dynamics_cases.py):
 //   int64  hdr[8] = { magic 'DYNCASE1', op, n, G, P, 0, 0, 0 }        n: lanes (op 0, 2), G: groups (op 1), P: track points (op 2)
@@ -20,17 +20,12 @@
 //         (0 when P < 5: car_reward does not call it then), its rel, within / dist / anchor of an unanchored within_track, and as raw 64-bit patterns the
 //         whole ring_candidates mask, the whole ring5_candidates mask and exec }
 // Every output buffer is filled with the byte 0xA5 first and carries `guard` extra entries; every launch has 64-lane workgroups, lanes past n return.
-#include <hip/hip_runtime.h>
+#include "kbench_dev.h"
 #include "../mpopis_amd/csrc/car_dynamics.h"
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <cmath>
-#include <vector>
 using namespace mpopis;
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 static const long long kMagicIn = 0x31455341434e5944ll, kMagicOut = 0x31305345524e5944ll;       // "DYNCASE1", "DYNRES01"
-static const int kGuard = 64, kPoison = 0xA5;
 enum { OP_PRIMS = 0, OP_STEP = 1, OP_REWARD = 2 };
 constexpr int kPrimIn = 14, kPrimOut = 16, kStepIn = 14, kStepOut = 12, kRewIn = 5, kRewOut = 12;
 
@@ -93,17 +88,6 @@ __global__ __launch_bounds__(64) void k_reward(CarParams p, Track tk, const doub
     o[11] = __longlong_as_double((long long)__builtin_amdgcn_read_exec());
 }
 
-template <class T> static bool rd(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-template <class T> static bool wr(FILE* f, const std::vector<T>& v) { return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
-template <class T> static hipError_t dpoison(T** p, size_t n) {              // n entries of poison
-    hipError_t e = hipMalloc(p, (n ? n : 1) * sizeof(T));
-    return e != hipSuccess ? e : hipMemset(*p, kPoison, (n ? n : 1) * sizeof(T));
-}
-template <class T> static hipError_t dupload(T** p, const std::vector<T>& v) {
-    hipError_t e = hipMalloc(p, (v.size() ? v.size() : 1) * sizeof(T));
-    return (e != hipSuccess || v.empty()) ? e : hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-template <class T> static hipError_t dfetch(std::vector<T>& v, const T* p, size_t n) { v.resize(n); return hipMemcpy(v.data(), p, n * sizeof(T), hipMemcpyDeviceToHost); }
 static int blocks(long long n) { return (int)((n + 63) / 64); }
 
 int main(int argc, char** argv) {
@@ -139,7 +123,7 @@ int main(int argc, char** argv) {
             else hipLaunchKernelGGL(k_step<false>, dim3(blocks(ng)), dim3(64), 0, s, p, d_in, d_out, ng, bnd[0], bnd[1], bnd[2], bnd[3], (int)gh[1]);
             CK(hipGetLastError()); CK(hipStreamSynchronize(s)); ++launches;
             outs.emplace_back(); CK(dfetch(outs.back(), d_out, (size_t)ng * kStepOut + kGuard));
-            CK(hipFree(d_in)); CK(hipFree(d_out));
+            CK(dfree_all());
         }
         if (fgetc(fi) != EOF) { printf("case file has the wrong length\n"); return 2; }
     } else {
@@ -148,14 +132,8 @@ int main(int argc, char** argv) {
         // the kernel indexes the tables with the anchor: only an anchor the host has validated gets near it
         for (long long i = 0; i < n; ++i) { const double a = in[(size_t)i * kRewIn + 4]; if (!(a >= -1.0 && a <= (double)(P - 1)) || a != floor(a)) { printf("invalid anchor in lane %lld\n", i); return 3; } }
         const CarParams p = make_car_params(p20.data());
-        std::vector<double> n2(P), nd, ring, cert; std::vector<int> ni;
-        for (long long i = 0; i < P; ++i) n2[i] = tx[i] * tx[i] + ty[i] * ty[i];
-        build_track_tables((int)P, tx.data(), ty.data(), nd, ni);
-        build_track_ring((int)P, tx.data(), ty.data(), tw.data(), n2.data(), nd, ring, cert);
-        double *d_x, *d_y, *d_w, *d_n2, *d_nd, *d_ring, *d_cert, *d_in, *d_out; int* d_ni;
-        CK(dupload(&d_x, tx)); CK(dupload(&d_y, ty)); CK(dupload(&d_w, tw)); CK(dupload(&d_n2, n2)); CK(dupload(&d_nd, nd)); CK(dupload(&d_ni, ni));
-        CK(dupload(&d_ring, ring)); CK(dupload(&d_cert, cert)); CK(dupload(&d_in, in)); CK(dpoison(&d_out, (size_t)n * kRewOut + kGuard));
-        const Track tk{d_x, d_y, d_w, d_n2, (int)P, d_ni, d_nd, std::min<int>(kTrackNbrW, (int)P), d_ring, d_cert};
+        Track tk; double *d_in, *d_out;
+        CK(dtrack(&tk, TrackHost((int)P, tx.data(), ty.data(), tw.data()))); CK(dupload(&d_in, in)); CK(dpoison(&d_out, (size_t)n * kRewOut + kGuard));
         hipLaunchKernelGGL(k_reward, dim3(blocks(n)), dim3(64), 0, s, p, tk, d_in, d_out, (int)n);
         CK(hipGetLastError()); CK(hipStreamSynchronize(s)); ++launches;
         outs.emplace_back(); CK(dfetch(outs.back(), d_out, (size_t)n * kRewOut + kGuard));

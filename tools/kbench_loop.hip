@@ -2,8 +2,8 @@
 // launch_harness_update (kernels_harness.hip), launch_trace_start / _step / _reorder (kernels_trace.hip), launch_plan_select / _assemble
 // (kernels_plan.hip) -- on the launches of a case file and writes the raw device outputs back to a file (dev / test tool, not shipped).  It holds no
 // reference arithmetic: tests/test_gpu_loop_harness.py writes the case, reads the result and compares with tests/helpers/loop_cases.py.  It calls
-// only launchers of engine.h and builds the device Track the way tools/kbench_rollout.hip does.
-// build: tools/build_kbench_loop.sh        run: tools/kbench_loop_bin <case file> <result file>
+// only launchers of engine.h; the device Track is car_dynamics.h's TrackHost, as mpopis_set_track uploads it (kbench_dev.h: dtrack).
+// build: tools/build_kbench.sh loop       run: tools/kbench_loop_bin <case file> <result file>
 //
 // case file (little endian; written by tests/helpers/loop_cases.py):
 //   int64  hdr[2] = { magic 'LOPCASE1', n_launches }
@@ -35,59 +35,11 @@
 #include "../mpopis_amd/csrc/engine.h"
 #include "../mpopis_amd/csrc/philox.h"      // kRngTabDoubles
 #include <algorithm>
-#include <cstdio>
+#include "kbench_dev.h"
 #include <cstdlib>
 #include <cmath>
-#include <vector>
 using namespace mpopis;
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
-#define BAD(msg) do { printf("%s (line %d)\n", msg, __LINE__); return 2; } while (0)
-static const int kGuard = 64, kPoison = 0xA5;
 enum { OP_STEP = 0, OP_LOOP = 1, OP_PLAN = 2, OP_REORDER = 3 };
-
-struct Arr { long long type = 0, count = 0; std::vector<char> bytes; };
-static size_t tsize(long long t) { return t == 1 ? 4 : 8; }
-static bool rd_ll(FILE* f, long long* v, size_t n) { return n == 0 || fread(v, 8, n, f) == n; }
-static std::vector<void*> g_allocs;                                       // freed after every launch of the file
-static hipError_t dmalloc(void** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 8);
-    if (e == hipSuccess) g_allocs.push_back(*p);
-    return e;
-}
-// device buffer of n entries (+ guard), poisoned; init (nullable): its first n entries
-template <class T> static hipError_t dout(T** p, size_t n, const void* init = nullptr) {
-    hipError_t e = dmalloc((void**)p, (n + kGuard) * sizeof(T));
-    if (e != hipSuccess) return e;
-    e = hipMemset(*p, kPoison, (n + kGuard) * sizeof(T));
-    if (e != hipSuccess || !init || !n) return e;
-    return hipMemcpy(*p, init, n * sizeof(T), hipMemcpyHostToDevice);
-}
-template <class T> static hipError_t dup(T** p, const Arr& a) {          // nullptr when the array is not given
-    *p = nullptr;
-    if (!a.count) return hipSuccess;
-    hipError_t e = dmalloc((void**)p, a.bytes.size());
-    return e != hipSuccess ? e : hipMemcpy(*p, a.bytes.data(), a.bytes.size(), hipMemcpyHostToDevice);
-}
-template <class T> static hipError_t dupv(T** p, const std::vector<T>& v) {
-    hipError_t e = dmalloc((void**)p, v.size() * sizeof(T));
-    return (e != hipSuccess || v.empty()) ? e : hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-struct Out { long long type; size_t count; const void* dev; };            // dev == nullptr: written as "not given"
-
-// the device Track of mpopis_set_track (engine_api.hip): coordinates, |q|^2, neighbour tables, ring table + certificates
-static hipError_t make_track(Track* tk, int P, const double* x, const double* y, const double* w) {
-    std::vector<double> xy((size_t)4 * P), nd, ring, cert; std::vector<int> ni;
-    for (int i = 0; i < P; ++i) { xy[i] = x[i]; xy[P + i] = y[i]; xy[2 * P + i] = w[i]; xy[3 * P + i] = x[i] * x[i] + y[i] * y[i]; }
-    build_track_tables(P, x, y, nd, ni);
-    build_track_ring(P, x, y, w, xy.data() + 3 * P, nd, ring, cert);
-    const size_t nring = ring.size();
-    ring.insert(ring.end(), cert.begin(), cert.end());
-    double *d, *dnd, *dring; int* dni;
-    hipError_t e;
-    if ((e = dupv(&d, xy)) != hipSuccess || (e = dupv(&dnd, nd)) != hipSuccess || (e = dupv(&dni, ni)) != hipSuccess || (e = dupv(&dring, ring)) != hipSuccess) return e;
-    *tk = Track{d, d + P, d + 2 * P, d + 3 * P, P, dni, dnd, std::min<int>(kTrackNbrW, P), dring, dring + nring};
-    return hipSuccess;
-}
 
 // EnvDesc and SlotEnv of ops STEP and LOOP from ipar[0..2] and arrays 0..8; 0: fine, 1: HIP error (printed), 2: bad case
 static int make_env(const std::vector<long long>& ip, const std::vector<Arr>& A, long long B, EnvDesc* env, SlotEnv* senv) {
@@ -113,8 +65,8 @@ static int make_env(const std::vector<long long>& ip, const std::vector<Arr>& A,
     }
     env->car = make_car_params(f64(0));
     if (env->car.nsub < 1 || env->car.nsub > 1000) return 2;
-    hipError_t e = make_track(&env->track, (int)P, f64(1), f64(2), f64(3));
-    if (e != hipSuccess) { printf("HIP error %s in make_track\n", hipGetErrorString(e)); return 1; }
+    hipError_t e = dtrack(&env->track, TrackHost((int)P, f64(1), f64(2), f64(3)));
+    if (e != hipSuccess) { printf("HIP error %s in dtrack\n", hipGetErrorString(e)); return 1; }
     if (A[6].count) {
         if (!is(6, 0, B * kCarNParams)) return 2;
         std::vector<CarParams> cp((size_t)B);
@@ -135,7 +87,7 @@ static int make_env(const std::vector<long long>& ip, const std::vector<Arr>& A,
         std::vector<Track> tks((size_t)B);
         const double* q = f64(8);
         for (long long b = 0; b < B; ++b) {
-            if ((e = make_track(&tks[b], sp[b], q, q + sp[b], q + 2 * sp[b])) != hipSuccess) { printf("HIP error %s in make_track\n", hipGetErrorString(e)); return 1; }
+            if ((e = dtrack(&tks[b], TrackHost(sp[b], q, q + sp[b], q + 2 * sp[b]))) != hipSuccess) { printf("HIP error %s in dtrack\n", hipGetErrorString(e)); return 1; }
             q += 3 * sp[b];
         }
         Track* d;
@@ -147,36 +99,20 @@ static int make_env(const std::vector<long long>& ip, const std::vector<Arr>& A,
 
 int main(int argc, char** argv) {
     if (argc < 3) { printf("usage: %s <case file> <result file>\n", argv[0]); return 2; }
-    FILE* fi = fopen(argv[1], "rb");
-    if (!fi) BAD("cannot open the case file");
-    long long hdr[2];
-    const char magic_in[9] = "LOPCASE1", magic_out[9] = "LOPRES01";
-    if (!rd_ll(fi, hdr, 2) || memcmp(hdr, magic_in, 8) != 0 || hdr[1] < 1 || hdr[1] > 4096) BAD("bad case header");
-    const long long nL = hdr[1];
+    FILE* fi; long long nL = 0;
+    if (const char* err = open_case(argv[1], "LOPCASE1", &nL, &fi)) BAD(err);
     FILE* fo = fopen(argv[2], "wb");
     if (!fo) BAD("cannot write the result file");
-    long long oh[3] = {0, kGuard, nL};
-    memcpy(oh, magic_out, 8);
-    bool ok = fwrite(oh, 8, 3, fo) == 3;
+    const long long oh[3] = {magic_word("LOPRES01"), kGuard, nL};
+    bool ok = write_arrays(fo, oh, 3, {});
     hipStream_t s; CK(hipStreamCreate(&s));
     for (long long li = 0; li < nL; ++li) {
-        long long lh[5];
-        if (!rd_ll(fi, lh, 5)) BAD("short case file");
-        const int op = (int)lh[0]; const long long B = lh[1], nI = lh[2], nD = lh[3], nA = lh[4];
-        if (op < 0 || op > 3 || B < 1 || B > 256 || nI < 0 || nI > 16 || nD < 0 || nD > 16 || nA < 1 || nA > 24) BAD("case out of range");
-        std::vector<long long> ip(16, 0); std::vector<double> dp(16, 0.0);
-        if (!rd_ll(fi, ip.data(), nI) || (nD && fread(dp.data(), 8, nD, fi) != (size_t)nD)) BAD("short case file");
-        std::vector<Arr> A(24);
-        for (long long i = 0; i < nA; ++i) {
-            long long h[2];
-            if (!rd_ll(fi, h, 2) || h[0] < 0 || h[0] > 2 || h[1] < 0 || h[1] > (1ll << 26)) BAD("bad array header");
-            A[i].type = h[0]; A[i].count = h[1]; A[i].bytes.resize((size_t)h[1] * tsize(h[0]));
-            if (h[1] && fread(A[i].bytes.data(), 1, A[i].bytes.size(), fi) != A[i].bytes.size()) BAD("short case file");
-        }
-        auto need = [&](int i, long long type, long long count, bool optional) {
-            return (optional && A[i].count == 0) || (A[i].type == type && A[i].count == count);
-        };
-        auto host = [&](int i) { return (const void*)A[i].bytes.data(); };
+        Launch L;
+        if (const char* err = read_launch(fi, CaseLimits{3, 1, 256, 24, 2, 1ll << 26}, &L)) BAD(err);
+        const int op = L.op; const long long B = L.B;
+        const std::vector<long long>& ip = L.ip; const std::vector<double>& dp = L.dp; const std::vector<Arr>& A = L.A;
+        auto need = [&](int i, long long type, long long count, bool optional) { return L.need(i, type, count, optional); };
+        auto host = [&](int i) { return L.host(i); };
         std::vector<Out> outs;
         if (op == OP_STEP || op == OP_LOOP) {
             EnvDesc env; SlotEnv senv;
@@ -290,19 +226,10 @@ int main(int argc, char** argv) {
         }
         CK(hipGetLastError()); CK(hipStreamSynchronize(s));
         const long long rh[2] = {op, (long long)outs.size()};
-        ok = ok && fwrite(rh, 8, 2, fo) == 2;
-        for (const Out& o : outs) {
-            const size_t cnt = o.dev ? o.count + kGuard : 0, bytes = cnt * tsize(o.type);
-            std::vector<char> h(bytes);
-            if (bytes) CK(hipMemcpy(h.data(), o.dev, bytes, hipMemcpyDeviceToHost));
-            const long long ah[2] = {o.type, (long long)cnt};
-            ok = ok && fwrite(ah, 8, 2, fo) == 2 && (bytes == 0 || fwrite(h.data(), 1, bytes, fo) == bytes);
-        }
-        for (void* p : g_allocs) CK(hipFree(p));
-        g_allocs.clear();
+        if (const int rc = write_back(fo, rh, 2, outs)) return rc;
+        CK(dfree_all());
     }
-    if (fgetc(fi) != EOF) BAD("case file has the wrong length");
-    fclose(fi);
+    if (const char* err = close_case(fi)) BAD(err);
     if (!ok || fclose(fo) != 0) BAD("write failed");
     printf("launches %lld\n", nL);
     return 0;

@@ -2,7 +2,7 @@
 // scatter in every partial-kernel form with its finish kernel, the shrinkage kernels, both CE updates, the gather / mean helpers) on the inputs of a
 // case file and writes the raw device outputs back to a file (dev / test tool, not shipped).  It holds no reference arithmetic:
 // tests/test_gpu_mfma_harness.py writes the case, reads the result and compares with NumPy longdouble and the oracle.
-// build: tools/build_kbench_mfma.sh        run: tools/kbench_mfma_bin <case file> <result file>
+// build: tools/build_kbench.sh mfma       run: tools/kbench_mfma_bin <case file> <result file>
 //
 // case file (little endian; written by tests/helpers/mfma_cases.py):
 //   int64  hdr[6] = { magic 'MFMCASE1', op, B, n_ipar, n_dpar, n_arrays }
@@ -28,62 +28,22 @@
 //                  arrays: active, X, idx, w, shiftA, shiftB                                             -> Xout, shift, mu
 #include "../mpopis_amd/csrc/engine.h"
 #include "../mpopis_amd/csrc/philox.h"
-#include <cstdio>
+#include "kbench_dev.h"
 #include <cstdlib>
 #include <cmath>
-#include <vector>
 using namespace mpopis;
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
-#define BAD(msg) do { printf("%s\n", msg); return 2; } while (0)
-static const int kGuard = 64, kPoison = 0xA5;
 enum { OP_TRMM = 0, OP_FUSED = 1, OP_TWOKERNEL = 2, OP_WCOV = 3, OP_SHRINK = 4, OP_CE_SMALL = 5, OP_CE_GENERAL = 6, OP_GATHER = 7 };
-
-struct Arr { long long type = 0, count = 0; std::vector<char> bytes; };
-static size_t tsize(long long t) { return t == 1 ? 4 : 8; }
-static bool rd_ll(FILE* f, long long* v, size_t n) { return n == 0 || fread(v, 8, n, f) == n; }
-// device buffer of n entries (+ guard), poisoned; init (nullable): its first n entries
-template <class T> static hipError_t dout(T** p, size_t n, const Arr* init = nullptr) {
-    hipError_t e = hipMalloc(p, (n + kGuard) * sizeof(T));
-    if (e != hipSuccess) return e;
-    e = hipMemset(*p, kPoison, (n + kGuard) * sizeof(T));
-    if (e != hipSuccess || !init || !init->count) return e;
-    return hipMemcpy(*p, init->bytes.data(), n * sizeof(T), hipMemcpyHostToDevice);
-}
-template <class T> static hipError_t dup(T** p, const Arr& a) {          // nullptr when the array is not given
-    *p = nullptr;
-    if (!a.count) return hipSuccess;
-    hipError_t e = hipMalloc(p, a.bytes.size());
-    return e != hipSuccess ? e : hipMemcpy(*p, a.bytes.data(), a.bytes.size(), hipMemcpyHostToDevice);
-}
-template <class T> static hipError_t dfill(T** p, size_t n, int byte) {
-    hipError_t e = hipMalloc(p, (n ? n : 1) * sizeof(T));
-    return e != hipSuccess ? e : hipMemset(*p, byte, (n ? n : 1) * sizeof(T));
-}
-struct Out { long long type; size_t count; const void* dev; bool guarded = true; };
 
 int main(int argc, char** argv) {
     if (argc < 3) { printf("usage: %s <case file> <result file>\n", argv[0]); return 2; }
-    FILE* fi = fopen(argv[1], "rb");
-    if (!fi) BAD("cannot open the case file");
-    long long hdr[6];
-    const char magic_in[9] = "MFMCASE1", magic_out[9] = "MFMRES01";
-    if (!rd_ll(fi, hdr, 6) || memcmp(hdr, magic_in, 8) != 0) BAD("bad case header");
-    const int op = (int)hdr[1]; const long long B = hdr[2], nI = hdr[3], nD = hdr[4], nA = hdr[5];
-    if (op < 0 || op > 7 || B < 1 || B > 8 || nI < 0 || nI > 16 || nD < 0 || nD > 16 || nA < 1 || nA > 16) BAD("case out of range");
-    std::vector<long long> ip(16, 0); std::vector<double> dp(16, 0.0);
-    if (!rd_ll(fi, ip.data(), nI) || (nD && fread(dp.data(), 8, nD, fi) != (size_t)nD)) BAD("short case file");
-    std::vector<Arr> A(16);
-    for (long long i = 0; i < nA; ++i) {
-        long long h[2];
-        if (!rd_ll(fi, h, 2) || h[0] < 0 || h[0] > 2 || h[1] < 0 || h[1] > (1ll << 28)) BAD("bad array header");
-        A[i].type = h[0]; A[i].count = h[1]; A[i].bytes.resize((size_t)h[1] * tsize(h[0]));
-        if (h[1] && fread(A[i].bytes.data(), 1, A[i].bytes.size(), fi) != A[i].bytes.size()) BAD("short case file");
-    }
-    if (fgetc(fi) != EOF) BAD("case file has the wrong length");
-    fclose(fi);
-    auto need = [&](int i, long long type, long long count, bool optional) {
-        return (optional && A[i].count == 0) || (A[i].type == type && A[i].count == count);
-    };
+    FILE* fi; Launch L;
+    const char* err = open_case(argv[1], "MFMCASE1", nullptr, &fi);
+    if (!err) err = read_launch(fi, CaseLimits{7, 1, 8, 16, 2, 1ll << 28, 0}, &L);
+    if (!err) err = close_case(fi);
+    if (err) BAD(err);
+    const int op = L.op; const long long B = L.B, nD = L.nD;
+    const std::vector<long long>& ip = L.ip; const std::vector<double>& dp = L.dp; const std::vector<Arr>& A = L.A;
+    auto need = [&](int i, long long type, long long count, bool optional) { return L.need(i, type, count, optional); };
     if (!need(0, 1, B, false)) BAD("active[B] missing");
 
     hipStream_t s; CK(hipStreamCreate(&s));
@@ -199,17 +159,9 @@ int main(int argc, char** argv) {
     CK(hipGetLastError()); CK(hipStreamSynchronize(s));
     FILE* fo = fopen(argv[2], "wb");
     if (!fo) BAD("cannot write the result file");
-    long long oh[4] = {0, form, kGuard, (long long)outs.size()};
-    memcpy(oh, magic_out, 8);
-    bool ok = fwrite(oh, 8, 4, fo) == 4;
-    for (const Out& o : outs) {
-        const size_t cnt = o.count + (o.guarded ? kGuard : 0), bytes = cnt * tsize(o.type);
-        std::vector<char> h(bytes);
-        CK(hipMemcpy(h.data(), o.dev, bytes, hipMemcpyDeviceToHost));
-        const long long ah[2] = {o.type, (long long)cnt};
-        ok = ok && fwrite(ah, 8, 2, fo) == 2 && (bytes == 0 || fwrite(h.data(), 1, bytes, fo) == bytes);
-    }
-    if (!ok || fclose(fo) != 0) BAD("write failed");
+    const long long oh[4] = {magic_word("MFMRES01"), form, kGuard, (long long)outs.size()};
+    if (const int rc = write_back(fo, oh, 4, outs)) return rc;
+    if (fclose(fo) != 0) BAD("write failed");
     printf("op %d B %lld form %lld\n", op, B, form);
     return 0;
 }

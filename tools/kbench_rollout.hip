@@ -3,7 +3,7 @@
 // tool, not shipped).  It holds no reference arithmetic: tests/test_gpu_rollout_harness.py writes the case, reads the result and compares with the
 // oracle, NumPy longdouble and exact invariants.  It calls only launchers of engine.h; the launches of one file share the process and therefore the
 // settings read once per process (MPOPIS_ROLLOUT_DUO, MPOPIS_COOP_MAX_WG).
-// build: tools/build_kbench_rollout.sh        run: tools/kbench_rollout_bin <case file> <result file>
+// build: tools/build_kbench.sh rollout       run: tools/kbench_rollout_bin <case file> <result file>
 //
 // case file (little endian; written by tests/helpers/rollout_cases.py):
 //   int64  hdr[2] = { magic 'ROLCASE1', n_launches }
@@ -23,92 +23,28 @@
 //               arrays: alive, status (before), iters (before), iters_acc (before), U, x [B][ncars][8], tx, ty, tw, cmin (before)
 //               -> status, active, iters, iters_acc, Uin, Ucur, cmin, xext (launch_step_begin), xext (launch_extend_state on the same x)
 #include "../mpopis_amd/csrc/engine.h"
-#include <cstdio>
+#include "kbench_dev.h"
 #include <cstdlib>
 #include <cmath>
-#include <vector>
 using namespace mpopis;
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
-#define BAD(msg) do { printf("%s\n", msg); return 2; } while (0)
-static const int kGuard = 64, kPoison = 0xA5;
 enum { OP_ROLLOUT = 0, OP_BEGIN = 1 };
-
-struct Arr { long long type = 0, count = 0; std::vector<char> bytes; };
-static size_t tsize(long long t) { return t == 1 ? 4 : 8; }
-static bool rd_ll(FILE* f, long long* v, size_t n) { return n == 0 || fread(v, 8, n, f) == n; }
-static std::vector<void*> g_allocs;                                       // freed after every launch of the file
-static hipError_t dmalloc(void** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 8);
-    if (e == hipSuccess) g_allocs.push_back(*p);
-    return e;
-}
-// device buffer of n entries (+ guard), poisoned; init (nullable): its first n entries
-template <class T> static hipError_t dout(T** p, size_t n, const Arr* init = nullptr) {
-    hipError_t e = dmalloc((void**)p, (n + kGuard) * sizeof(T));
-    if (e != hipSuccess) return e;
-    e = hipMemset(*p, kPoison, (n + kGuard) * sizeof(T));
-    if (e != hipSuccess || !init || !init->count) return e;
-    return hipMemcpy(*p, init->bytes.data(), n * sizeof(T), hipMemcpyHostToDevice);
-}
-template <class T> static hipError_t dup(T** p, const Arr& a) {          // nullptr when the array is not given
-    *p = nullptr;
-    if (!a.count) return hipSuccess;
-    hipError_t e = dmalloc((void**)p, a.bytes.size());
-    return e != hipSuccess ? e : hipMemcpy(*p, a.bytes.data(), a.bytes.size(), hipMemcpyHostToDevice);
-}
-template <class T> static hipError_t dupv(T** p, const std::vector<T>& v) {
-    hipError_t e = dmalloc((void**)p, v.size() * sizeof(T));
-    return (e != hipSuccess || v.empty()) ? e : hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-struct Out { long long type; size_t count; const void* dev; };            // dev == nullptr: written as "not given"
-
-// the device Track of mpopis_set_track (engine_api.hip): coordinates, |q|^2, neighbour tables, ring table + certificates
-static hipError_t make_track(Track* tk, int P, const double* x, const double* y, const double* w) {
-    std::vector<double> xy((size_t)4 * P), nd, ring, cert; std::vector<int> ni;
-    for (int i = 0; i < P; ++i) { xy[i] = x[i]; xy[P + i] = y[i]; xy[2 * P + i] = w[i]; xy[3 * P + i] = x[i] * x[i] + y[i] * y[i]; }
-    build_track_tables(P, x, y, nd, ni);
-    build_track_ring(P, x, y, w, xy.data() + 3 * P, nd, ring, cert);
-    const size_t nring = ring.size();
-    ring.insert(ring.end(), cert.begin(), cert.end());
-    double *d, *dnd, *dring; int* dni;
-    hipError_t e;
-    if ((e = dupv(&d, xy)) != hipSuccess || (e = dupv(&dnd, nd)) != hipSuccess || (e = dupv(&dni, ni)) != hipSuccess || (e = dupv(&dring, ring)) != hipSuccess) return e;
-    *tk = Track{d, d + P, d + 2 * P, d + 3 * P, P, dni, dnd, std::min<int>(kTrackNbrW, P), dring, dring + nring};
-    return hipSuccess;
-}
 
 int main(int argc, char** argv) {
     if (argc < 3) { printf("usage: %s <case file> <result file>\n", argv[0]); return 2; }
-    FILE* fi = fopen(argv[1], "rb");
-    if (!fi) BAD("cannot open the case file");
-    long long hdr[2];
-    const char magic_in[9] = "ROLCASE1", magic_out[9] = "ROLRES01";
-    if (!rd_ll(fi, hdr, 2) || memcmp(hdr, magic_in, 8) != 0 || hdr[1] < 1 || hdr[1] > 4096) BAD("bad case header");
-    const long long nL = hdr[1];
+    FILE* fi; long long nL = 0;
+    if (const char* err = open_case(argv[1], "ROLCASE1", &nL, &fi)) BAD(err);
     FILE* fo = fopen(argv[2], "wb");
     if (!fo) BAD("cannot write the result file");
-    long long oh[3] = {0, kGuard, nL};
-    memcpy(oh, magic_out, 8);
-    bool ok = fwrite(oh, 8, 3, fo) == 3;
+    const long long oh[3] = {magic_word("ROLRES01"), kGuard, nL};
+    bool ok = write_arrays(fo, oh, 3, {});
     hipStream_t s; CK(hipStreamCreate(&s));
     for (long long li = 0; li < nL; ++li) {
-        long long lh[5];
-        if (!rd_ll(fi, lh, 5)) BAD("short case file");
-        const int op = (int)lh[0]; const long long B = lh[1], nI = lh[2], nD = lh[3], nA = lh[4];
-        if (op < 0 || op > 1 || B < 1 || B > 8 || nI < 0 || nI > 16 || nD < 0 || nD > 16 || nA < 1 || nA > 16) BAD("case out of range");
-        std::vector<long long> ip(16, 0); std::vector<double> dp(16, 0.0);
-        if (!rd_ll(fi, ip.data(), nI) || (nD && fread(dp.data(), 8, nD, fi) != (size_t)nD)) BAD("short case file");
-        std::vector<Arr> A(16);
-        for (long long i = 0; i < nA; ++i) {
-            long long h[2];
-            if (!rd_ll(fi, h, 2) || h[0] < 0 || h[0] > 2 || h[1] < 0 || h[1] > (1ll << 28)) BAD("bad array header");
-            A[i].type = h[0]; A[i].count = h[1]; A[i].bytes.resize((size_t)h[1] * tsize(h[0]));
-            if (h[1] && fread(A[i].bytes.data(), 1, A[i].bytes.size(), fi) != A[i].bytes.size()) BAD("short case file");
-        }
-        auto need = [&](int i, long long type, long long count, bool optional) {
-            return (optional && A[i].count == 0) || (A[i].type == type && A[i].count == count);
-        };
-        auto f64 = [&](int i) { return (const double*)A[i].bytes.data(); };
+        Launch L;
+        if (const char* err = read_launch(fi, CaseLimits{1, 1, 8, 16, 2}, &L)) BAD(err);
+        const int op = L.op; const long long B = L.B;
+        const std::vector<long long>& ip = L.ip; const std::vector<double>& dp = L.dp; const std::vector<Arr>& A = L.A;
+        auto need = [&](int i, long long type, long long count, bool optional) { return L.need(i, type, count, optional); };
+        auto f64 = [&](int i) { return L.f64(i); };
         long long form[4] = {0, 0, 0, 0};
         std::vector<Out> outs;
         if (op == OP_ROLLOUT) {
@@ -126,7 +62,7 @@ int main(int argc, char** argv) {
             if (car) {
                 a.env.car = make_car_params(f64(1));
                 if (a.env.car.nsub < 1 || a.env.car.nsub > 1000) BAD("sub-step count out of range");
-                CK(make_track(&a.env.track, (int)P, f64(2), f64(3), f64(4)));
+                CK(dtrack(&a.env.track, TrackHost((int)P, f64(2), f64(3), f64(4))));
             } else if (kind == MPOPIS_ENV_CARTPOLE) a.env.cp = make_cp_params(f64(1));
             else a.env.mc = make_mc_params(f64(1));
             for (int i = 0; i < as; ++i) { a.env.lo[i] = f64(5)[i]; a.env.hi[i] = f64(6)[i]; }
@@ -160,7 +96,7 @@ int main(int argc, char** argv) {
             if (!need(0, 1, B, true) || !need(1, 1, B, true) || !need(2, 1, B, false) || !need(3, 2, B, true) || !need(4, 0, B * cs, false) || !need(5, 0, B * ncars * 8, true) ||
                 !need(6, 0, P, false) || !need(7, 0, P, false) || !need(8, 0, P, false) || !need(9, 2, B, true)) BAD("wrong array sizes");
             Track tk{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr};
-            if (P > 0) CK(make_track(&tk, (int)P, f64(6), f64(7), f64(8)));
+            if (P > 0) CK(dtrack(&tk, TrackHost((int)P, f64(6), f64(7), f64(8))));
             int *d_alive, *d_status = nullptr, *d_active, *d_iters; unsigned long long *d_acc = nullptr, *d_cmin = nullptr; double *d_U, *d_x, *d_Uin, *d_Ucur, *d_xext = nullptr, *d_xref = nullptr;
             CK(dup(&d_alive, A[0])); CK(dup(&d_U, A[4])); CK(dup(&d_x, A[5]));
             if (A[1].count) CK(dout(&d_status, (size_t)B, &A[1]));
@@ -176,19 +112,10 @@ int main(int argc, char** argv) {
         }
         CK(hipGetLastError()); CK(hipStreamSynchronize(s));
         const long long rh[6] = {op, form[0], form[1], form[2], form[3], (long long)outs.size()};
-        ok = ok && fwrite(rh, 8, 6, fo) == 6;
-        for (const Out& o : outs) {
-            const size_t cnt = o.dev ? o.count + kGuard : 0, bytes = cnt * tsize(o.type);
-            std::vector<char> h(bytes);
-            if (bytes) CK(hipMemcpy(h.data(), o.dev, bytes, hipMemcpyDeviceToHost));
-            const long long ah[2] = {o.type, (long long)cnt};
-            ok = ok && fwrite(ah, 8, 2, fo) == 2 && (bytes == 0 || fwrite(h.data(), 1, bytes, fo) == bytes);
-        }
-        for (void* p : g_allocs) CK(hipFree(p));
-        g_allocs.clear();
+        if (const int rc = write_back(fo, rh, 6, outs)) return rc;
+        CK(dfree_all());
     }
-    if (fgetc(fi) != EOF) BAD("case file has the wrong length");
-    fclose(fi);
+    if (const char* err = close_case(fi)) BAD(err);
     if (!ok || fclose(fo) != 0) BAD("write failed");
     printf("launches %lld\n", nL);
     return 0;

@@ -3,7 +3,7 @@
 // memory, philox_normal_quad / philox_normal_pair with a 64-bit counter) on the inputs of a case file and writes the raw device outputs back to a
 // file (dev / test tool, not shipped).  It holds no reference arithmetic: tests/test_gpu_sample_harness.py writes the case, reads the result and
 // compares with the oracle and NumPy.  It calls only launchers declared in engine.h, plus the probe kernels below.
-// build: tools/build_kbench_sample.sh        run: tools/kbench_sample_bin <case file> <result file>
+// build: tools/build_kbench.sh sample       run: tools/kbench_sample_bin <case file> <result file>
 //
 // case file (little endian; layout shared with tests/helpers/sample_cases.py):
 //   int64  hdr[16] = { magic 'SMPCASE1', op, B, cs, K, as, T, mppi_order, flags, n, slo, shi, src_stride, src_off, 0, 0 }
@@ -26,13 +26,10 @@
 // Every output buffer is filled with the byte 0xA5 first (and carries `guard` extra entries), so the test sees what the launch left untouched.
 #include "../mpopis_amd/csrc/engine.h"
 #include "../mpopis_amd/csrc/philox.h"
-#include <cstdio>
+#include "kbench_dev.h"
 #include <cstdlib>
-#include <vector>
 using namespace mpopis;
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 static const long long kMagicIn = 0x3145534143504d53ll, kMagicOut = 0x3130534552504d53ll;       // "SMPCASE1", "SMPRES01"
-static const int kGuard = 64, kPoison = 0xA5;
 enum { OP_TAB = 0, OP_WORDS = 1, OP_BOXMULLER = 2, OP_NORMALQ = 3, OP_NORMALS = 4, OP_DRAWS = 5, OP_FINALIZE = 6, OP_T_IN = 7, OP_T_OUT = 8 };
 
 // ---- probe kernels over philox.h ---------------------------------------------------------------------------------------------------------
@@ -71,17 +68,6 @@ __global__ void __launch_bounds__(256) k_probe_normalq(const uint64_t* __restric
     for (int e = 0; e < 8; ++e) z[8 * i + e] = o[e];
 }
 
-template <class T> static bool rd(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-template <class T> static bool wr(FILE* f, const std::vector<T>& v) { return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
-template <class T> static hipError_t dpoison(T** p, size_t n) {              // n entries of poison
-    hipError_t e = hipMalloc(p, (n ? n : 1) * sizeof(T));
-    return e != hipSuccess ? e : hipMemset(*p, kPoison, (n ? n : 1) * sizeof(T));
-}
-template <class T> static hipError_t dupload(T** p, const std::vector<T>& v, size_t guard = 0) {        // v, then `guard` entries of poison
-    hipError_t e = dpoison(p, v.size() + guard);
-    return (e != hipSuccess || v.empty()) ? e : hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-template <class T> static hipError_t dfetch(std::vector<T>& v, const T* p, size_t n) { v.resize(n); return hipMemcpy(v.data(), p, n * sizeof(T), hipMemcpyDeviceToHost); }
 
 int main(int argc, char** argv) {
     if (argc < 3) { printf("usage: %s <case file> <result file>\n", argv[0]); return 2; }

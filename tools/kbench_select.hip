@@ -1,7 +1,7 @@
 // kbench_select.hip -- runs ONE launch of a selection kernel (sort + elite early break, alias table, alias draw, softmax weights, the CE kernel's
 // fused sort) on the inputs of a case file and writes the raw device outputs back to a file (dev / test tool, not shipped).
 // It holds no reference arithmetic: tests/test_gpu_select_harness.py writes the case, reads the result and compares with the oracle and NumPy.
-// build: tools/build_kbench_select.sh        run: tools/kbench_select_bin <case file> <result file>
+// build: tools/build_kbench.sh select       run: tools/kbench_select_bin <case file> <result file>
 //
 // case file (little endian; layout shared with tests/helpers/select_cases.py):
 //   int64  hdr[8]  = { magic 'SELCASE1', op, B, K, m_elite, flags, di_stride, log_stride }      flags bit 0: run WITHOUT the workspaces (nullptr)
@@ -19,27 +19,13 @@
 //   op 3:     double w[B K + guard], wsum[B]; int32 status[B]
 // Every output buffer is filled with the byte 0xA5 first (and carries `guard` extra entries), so the test sees what the launch left untouched.
 #include "../mpopis_amd/csrc/engine.h"
-#include <cstdio>
+#include "kbench_dev.h"
 #include <cstdlib>
 #include <cmath>
-#include <vector>
 using namespace mpopis;
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 static const long long kMagicIn = 0x31455341434c4553ll, kMagicOut = 0x31305345524c4553ll;       // "SELCASE1", "SELRES01"
-static const int kGuard = 64, kPoison = 0xA5;
 enum { OP_SORT = 0, OP_ALIAS_BUILD = 1, OP_ALIAS_SAMPLE = 2, OP_WEIGHTS = 3, OP_CE_SORT = 4 };
 
-template <class T> static bool rd(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-template <class T> static bool wr(FILE* f, const std::vector<T>& v) { return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
-template <class T> static hipError_t dpoison(T** p, size_t n) {              // n entries of poison
-    hipError_t e = hipMalloc(p, (n ? n : 1) * sizeof(T));
-    return e != hipSuccess ? e : hipMemset(*p, kPoison, (n ? n : 1) * sizeof(T));
-}
-template <class T> static hipError_t dupload(T** p, const std::vector<T>& v) {
-    hipError_t e = hipMalloc(p, (v.size() ? v.size() : 1) * sizeof(T));
-    return (e != hipSuccess || v.empty()) ? e : hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-template <class T> static hipError_t dfetch(std::vector<T>& v, const T* p, size_t n) { v.resize(n); return hipMemcpy(v.data(), p, n * sizeof(T), hipMemcpyDeviceToHost); }
 
 int main(int argc, char** argv) {
     if (argc < 3) { printf("usage: %s <case file> <result file>\n", argv[0]); return 2; }
