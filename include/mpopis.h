@@ -75,7 +75,11 @@ extern "C" {
  *    Later gained ONE more entry point, mpopis_run_trials_traced, and the struct mpopis_trace it takes: the closed loop of mpopis_run_trials that
  *    also records each step's driven state, reward, iteration count, lane / β read-out and, every plan_every steps, the plan of mpopis_get_plan,
  *    all from inside the resident loop.  mpopis_config and every other entry point are unchanged, mpopis_run_trials enqueues what it enqueued
- *    before; a library that predates it does not export the symbol, which is how a caller detects support. */
+ *    before; a library that predates it does not export the symbol, which is how a caller detects support.
+ *    Later gained ONE more entry point, mpopis_set_env_params_cars: one parameter vector per CAR of a multi-car slot, as every env.envs[i] of the
+ *    reference's MultiCarRacingEnv owns its params (a heavy car beside a light one, worn tyres beside fresh ones).  mpopis_config and every other
+ *    entry point are unchanged, and a handle that never calls it launches what it launched before; a library that predates it does not export
+ *    the symbol, which is how a caller detects support (it gives every car of a slot the slot's one vector). */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -192,7 +196,7 @@ int  mpopis_set_track(mpopis_handle *h, const double *x, const double *y, const 
 /* Per-slot env parameters and tracks: slot b behaves like a handle given p[b*n .. b*n+n) through mpopis_set_env_params and track
  * track_of_slot[b] through mpopis_set_track.  They hold for mpopis_rollout_costs, mpopis_policy_step, mpopis_policy_call, mpopis_env_step,
  * mpopis_env_query, mpopis_run_trials and mpopis_bench_policy_steps.  Action bounds, K, H and N stay shared.
- *   mpopis_set_env_params_slots  B vectors of n doubles: n = 20 on a car handle (all cars of a multi-car slot share the slot's vector), 8 on
+ *   mpopis_set_env_params_slots  B vectors of n doubles: n = 20 on a car handle (all cars of a multi-car slot share the slot's vector; one per car: mpopis_set_env_params_cars), 8 on
  *                                MountainCar, 11 on CartPole.  MPOPIS_ERR_ARG: another n, NULL p, a custom handle (per-slot data of a custom
  *                                env goes through mpopis_set_env_table(..., per_slot)).  mpopis_set_env_params afterwards returns the handle
  *                                to one shared vector.
@@ -212,6 +216,22 @@ int  mpopis_set_track(mpopis_handle *h, const double *x, const double *y, const 
 int  mpopis_set_env_params_slots(mpopis_handle *h, const double *p /* B*n */, int32_t n);
 int  mpopis_set_tracks(mpopis_handle *h, int32_t ntracks, const int32_t *P, const double *x, const double *y, const double *w,
                        const int32_t *track_of_slot /* B or NULL */);
+/* A fleet: every car of a multi-car slot with its own parameter vector (MultiCarRacingEnv(N; car_params = [...]) and env.envs[i] of
+ * src/envs/multi-car_racing.jl:23-45; env(a) steps car i with its own params, reward(env) sums every car's own reward, :145-158, :200-207).
+ * Car handles only, n = MPOPIS_CAR_NPARAMS.
+ *   per_slot  0: p holds num_cars*20 doubles and every slot gets that fleet; otherwise B*num_cars*20.  Car c of slot b then behaves like a
+ *             CarRacingEnv constructed with p[(b*num_cars + c)*20 ..].
+ * It holds for mpopis_rollout_costs, mpopis_policy_step, mpopis_policy_call, mpopis_env_step, mpopis_env_query, mpopis_get_plan,
+ * mpopis_run_trials (a car counts as beyond the β limit when it exceeds ITS OWN), mpopis_run_trials_traced and mpopis_bench_policy_steps.
+ * dt and δt (entries 18, 19) must be equal across the cars of one slot -- a MultiCarRacingEnv has one of each -- and may differ between slots.
+ * A fleet handle runs a rollout kernel of its own (one wave per car); with equal vectors its costs agree with a shared handle's to rounding,
+ * not necessarily to the bit.  mpopis_set_env_params or mpopis_set_env_params_slots afterwards return the handle to one vector per slot, with
+ * the results of a handle that never had a fleet.  Independent of mpopis_set_track / mpopis_set_tracks: a fleet handle may carry per-slot tracks.
+ * On a num_cars == 1 handle the call is mpopis_set_env_params (per_slot == 0) or mpopis_set_env_params_slots.
+ * A setup call like mpopis_set_env_params_slots (waits for what is queued, allocates at the first call -- MPOPIS_ERR_HIP when that fails --, a
+ * refused or failed call leaves the handle as it was).  MPOPIS_ERR_ARG: another env kind, a custom handle, n != 20, NULL p, dt or δt that
+ * differ inside a slot (mpopis_last_error names the slot and the car). */
+int  mpopis_set_env_params_cars(mpopis_handle *h, const double *p /* [B*]num_cars*n */, int32_t n /* 20 */, int32_t per_slot);
 int  mpopis_set_action_bounds(mpopis_handle *h, const double *lo, const double *hi); /* action_space(env) */
 int  mpopis_reset(mpopis_handle *h);                       /* reset!(env) per slot: car_racing.jl:215-223, multi :160-180 */
 int  mpopis_set_state(mpopis_handle *h, const double *x /* B*ss */, const int32_t *t, const int32_t *done);

@@ -64,6 +64,10 @@ end
 car_param_vector(env::CarRacingEnv) = Float64[getfield(env.params, f) for f in fieldnames(typeof(env.params))] |>
                                       v -> vcat(v, env.dt, env.δt)
 car_param_vector(env::MultiCarRacingEnv) = car_param_vector(env.envs[1])
+# every env.envs[i] owns its params (multi-car_racing.jl:23-45): the vectors of all cars, one after the other, and whether they differ at all
+car_fleet_vectors(env::MultiCarRacingEnv) = [car_param_vector(en) for en in env.envs]
+is_fleet(env::MultiCarRacingEnv) = any(v -> v != car_param_vector(env.envs[1]), car_fleet_vectors(env))
+is_fleet(env) = false
 track_of(env::CarRacingEnv) = env.track
 track_of(env::MultiCarRacingEnv) = env.envs[1].track
 
@@ -92,6 +96,10 @@ function handle(pol, env)
         if kind == 1
             p = car_param_vector(env); tr = track_of(env)
             check(h, ccall((:mpopis_set_env_params, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32), h, p, length(p)))
+            if is_fleet(env)                             # cars with different params: one vector per car (a library without the symbol fails here, loudly)
+                pf = reduce(vcat, car_fleet_vectors(env))
+                check(h, ccall((:mpopis_set_env_params_cars, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32), h, pf, Int32(length(p)), Int32(0)))
+            end
             check(h, ccall((:mpopis_set_track, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32),
                            h, tr.x′, tr.y′, tr.lane_width′, length(tr.x′)))
         elseif kind == 2

@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "mpopis_timing_reset", "mpopis_bench_policy_steps",
     "mpopis_create_custom", "mpopis_set_env_table", "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
     "mpopis_set_slot_hyper", "mpopis_get_slot_hyper", "mpopis_set_Sigma_slots", "mpopis_set_env_params_slots", "mpopis_set_tracks",
-    "mpopis_get_plan", "mpopis_run_trials_traced",
+    "mpopis_get_plan", "mpopis_run_trials_traced", "mpopis_set_env_params_cars",
 ]
 
 
@@ -96,6 +96,8 @@ def lib():
             L.mpopis_get_plan.argtypes = [H, C.c_int32, _dp, _dp, _dp, _ip, _dp]
         if hasattr(L, "mpopis_run_trials_traced"):              # (the traced closed loop: newest)
             L.mpopis_run_trials_traced.argtypes = [H, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(Trace)]
+        if hasattr(L, "mpopis_set_env_params_cars"):            # (one parameter vector per car of a multi-car slot)
+            L.mpopis_set_env_params_cars.argtypes = [H, _dp, C.c_int32, C.c_int32]
         L.mpopis_destroy.argtypes = [H]
         L.mpopis_destroy.restype = None
         L.mpopis_set_env_params.argtypes = [H, _dp, C.c_int32]

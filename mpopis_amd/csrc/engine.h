@@ -88,7 +88,10 @@ struct SlotEnv {
     const CpParams* cp = nullptr;
     const Track* track = nullptr;
     size_t lds_all = 0, lds_ring = 0;
-    bool any() const { return car || mc || cp || track; }
+    // A fleet (mpopis_set_env_params_cars): [B][ncars] structs, car c of slot b at cars[b * ncars + c]; null: no fleet.  With it
+    // `track` is set too and `car` is null: the rollout runs the one-wave-per-car body (kernels_rollout_fleet.hip), the small kernels read cars[].
+    const CarParams* cars = nullptr;
+    bool any() const { return car || mc || cp || track || cars; }
 };
 // the small kernels (env step / query, harness bookkeeping, the simple envs' rollout) overwrite their by-value EnvDesc with slot b's parts
 __device__ __forceinline__ void slot_env_into(EnvDesc& env, const SlotEnv& se, int b) {
@@ -166,9 +169,14 @@ struct SlotVal { double v; const double* per_slot; };   // per_slot == nullptr: 
 // The kernel launch_rollout picks, as a pure function of the launch's arguments (the launcher switches on it; tools/kbench_rollout.hip writes it into
 // its result so that a test written for one form fails when a threshold moves): the body, whether the trajectory logger is on, whether every track
 // table is staged in LDS (car bodies: otherwise the ring table only; custom body: the env's data table goes to the code object's LDS kernel), and the dynamic LDS of one workgroup.  MPOPIS_ROLLOUT_DUO is read once per process.
-enum RolloutBody { ROLLOUT_SIMPLE2 = 0, ROLLOUT_SIMPLE4 = 1, ROLLOUT_CUSTOM = 2, ROLLOUT_TWO_WAVE = 3, ROLLOUT_ONE_WAVE_SPB1 = 4, ROLLOUT_ONE_WAVE_SPB4 = 5 };
+enum RolloutBody { ROLLOUT_SIMPLE2 = 0, ROLLOUT_SIMPLE4 = 1, ROLLOUT_CUSTOM = 2, ROLLOUT_TWO_WAVE = 3, ROLLOUT_ONE_WAVE_SPB1 = 4, ROLLOUT_ONE_WAVE_SPB4 = 5,
+                   ROLLOUT_FLEET = 6 /* one wave per car of 64 samples: a handle whose cars carry their own parameters */ };
 struct RolloutForm { RolloutBody body = ROLLOUT_SIMPLE2; bool log = false, tlds = false; size_t lds = 0; };
 RolloutForm rollout_form(const RolloutArgs& a);
+// kernels_rollout_fleet.hip: static LDS of the fleet body for ncars cars (the position exchange [2][ncars][2][64] doubles + the per-car action bounds),
+// which rollout_form counts against the default 64 KB, and its launcher (false: no kernel for this car count)
+constexpr size_t fleet_static_lds(int ncars) { return (size_t)ncars * (2 * 2 * 64 + 4) * sizeof(double); }
+bool launch_car_rollout_fleet(const RolloutArgs& a, const RolloutForm& f, hipStream_t st);
 bool launch_rollout(const RolloutArgs& a, hipStream_t s, hipError_t* custom_err = nullptr);      // false: nothing launched -- no rollout kernel for this env, or the custom env's launch failed (*custom_err says why)
 void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t s, const Track& tk, const Track* slot_tk = nullptr /* [B], or null: tk in every slot */);
 // (iters_acc: per-slot running sum of the iteration counts of earlier steps, folded in before iters is cleared; may be null)

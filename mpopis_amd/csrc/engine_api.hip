@@ -471,9 +471,9 @@ int mpopis_set_env_params(mpopis_handle* h, const double* p, int32_t n) {
         if (n != MPOPIS_MOUNTAINCAR_NPARAMS) { h->err = "MountainCar expects 8 parameters"; return MPOPIS_ERR_ARG; }
         h->env.mc = make_mc_params(p);
     }
-    if (h->env_params_slots_on || h->track_slots_on) {         // (after mpopis_set_env_params_slots: back to one shared vector)
+    if (h->env_params_slots_on || h->track_slots_on || h->fleet_on) {      // (after mpopis_set_env_params_slots / _cars: back to one shared vector)
         if (const int rc = quiesce(h)) return rc;
-        h->env_params_slots_on = false;
+        h->env_params_slots_on = false; h->fleet_on = false;
         return h->sync_slot_env();
     }
     return MPOPIS_OK;
@@ -482,7 +482,7 @@ int mpopis_set_env_params(mpopis_handle* h, const double* p, int32_t n) {
 // Car handles: while exactly one of the per-slot arrays is in force, fill the other with B copies of the shared value (engine_handle.h).  The caller
 // has quiesced the handle.  (A shared track that is not set yet gives descriptors with P = 0: track_missing() then refuses the calls that need one.)
 int mpopis_handle::sync_slot_env() {
-    if (env.kind != MPOPIS_ENV_CAR || env_params_slots_on == track_slots_on) return MPOPIS_OK;
+    if (env.kind != MPOPIS_ENV_CAR || (env_params_slots_on || fleet_on) == track_slots_on) return MPOPIS_OK;
     const char* msg = "hipMalloc of the per-slot env arrays failed";
     if (track_slots_on) {
         if (slot_alloc(d_car_sl, 1)) { (void)hipGetLastError(); err = msg; return MPOPIS_ERR_HIP; }
@@ -528,9 +528,44 @@ int mpopis_set_env_params_slots(mpopis_handle* h, const double* p, int32_t n) {
     else if (kind == MPOPIS_ENV_CARTPOLE) rc = upload(h->d_cp_sl, [](const double* q) { return make_cp_params(q); });
     else rc = upload(h->d_mc_sl, [](const double* q) { return make_mc_params(q); });
     if (rc) return rc;
-    const bool was = h->env_params_slots_on;
-    h->env_params_slots_on = true;
-    if ((rc = h->sync_slot_env())) h->env_params_slots_on = was;
+    const bool was = h->env_params_slots_on, was_fleet = h->fleet_on;
+    h->env_params_slots_on = true; h->fleet_on = false;        // (a fleet ends here: one vector per slot again)
+    if ((rc = h->sync_slot_env())) { h->env_params_slots_on = was; h->fleet_on = was_fleet; }
+    return rc;
+}
+
+// One parameter vector per CAR of a multi-car slot: env.envs[c] of the reference's MultiCarRacingEnv owns its params
+// (multi-car_racing.jl:23-45).  A setup call like the one above; the [B][num_cars] struct array and the [B] track array the fleet rollout reads
+// beside it are both allocated before either is written, so nothing fails past that point but a copy on a quiesced stream.
+int mpopis_set_env_params_cars(mpopis_handle* h, const double* p, int32_t n, int32_t per_slot) {
+    if (h) h->plan_drop("mpopis_set_env_params_cars");
+    if (!h) return MPOPIS_ERR_ARG;
+    if (!p) { h->err = "mpopis_set_env_params_cars: p is NULL"; return MPOPIS_ERR_ARG; }
+    if (h->env.kind == MPOPIS_ENV_CUSTOM) { h->err = "mpopis_set_env_params_cars: not for a custom handle (a custom env has no cars)"; return MPOPIS_ERR_ARG; }
+    if (h->env.kind != MPOPIS_ENV_CAR) { h->err = "mpopis_set_env_params_cars: not a car handle (only MultiCarRacingEnv holds several cars)"; return MPOPIS_ERR_ARG; }
+    if (n != MPOPIS_CAR_NPARAMS) { h->err = "mpopis_set_env_params_cars: a car expects 20 parameters, got n = " + std::to_string(n); return MPOPIS_ERR_ARG; }
+    const int B = h->B_full, NC = h->env.ncars;
+    if (NC == 1) return per_slot ? mpopis_set_env_params_slots(h, p, n) : mpopis_set_env_params(h, p, n);      // one car: the existing forms and kernels
+    const int nb = per_slot ? B : 1;
+    for (int b = 0; b < nb; ++b)
+        for (int c = 1; c < NC; ++c) {
+            const double *q0 = p + (size_t)b * NC * n, *q = q0 + (size_t)c * n;
+            if (q[18] != q0[18] || q[19] != q0[19]) {          // MultiCarRacingEnv has ONE dt / δt (:26-45)
+                h->err = "mpopis_set_env_params_cars: dt / δt of slot " + std::to_string(b) + ", car " + std::to_string(c) + " differ from those of the slot's car 0 (a MultiCarRacingEnv has one dt and one δt for all its cars)";
+                return MPOPIS_ERR_ARG;
+            }
+        }
+    if (const int rc = quiesce(h)) return rc;
+    std::vector<CarParams> host((size_t)B * NC);
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < NC; ++c) host[(size_t)b * NC + c] = make_car_params(p + ((size_t)(per_slot ? b : 0) * NC + c) * n);
+    if (h->slot_alloc(h->d_cars_sl, NC) || h->slot_alloc(h->d_track_sl, 1)) { (void)hipGetLastError(); h->err = "mpopis_set_env_params_cars: hipMalloc of the fleet's parameter array failed"; return MPOPIS_ERR_HIP; }
+    HIPCHK(h, hipMemcpyAsync(h->d_cars_sl, host.data(), sizeof(CarParams) * host.size(), hipMemcpyHostToDevice, h->stream));      // (behind the buffer's zero-fill)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const bool was = h->env_params_slots_on, was_fleet = h->fleet_on;
+    h->env_params_slots_on = false; h->fleet_on = true;
+    const int rc = h->sync_slot_env();
+    if (rc) { h->env_params_slots_on = was; h->fleet_on = was_fleet; }
     return rc;
 }
 
@@ -581,7 +616,7 @@ int mpopis_set_track(mpopis_handle* h, const double* x, const double* y, const d
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Track tk;
     if (const int rc = upload_track(h, x, y, w, P, &tk)) return rc;
-    if (h->env_params_slots_on || h->track_slots_on) {         // (after mpopis_set_tracks: back to one shared track)
+    if (h->env_params_slots_on || h->track_slots_on || h->fleet_on) {      // (after mpopis_set_tracks: back to one shared track)
         if (const int rc = quiesce(h)) return rc;
         h->env.track = tk;
         h->track_slots_on = false;

@@ -88,11 +88,18 @@ struct mpopis_handle {
     mpopis::Track* d_track_sl = nullptr;
     bool env_params_slots_on = false, track_slots_on = false;
     size_t track_sl_lds_all = 0, track_sl_lds_ring = 0;          // track_lds_bytes of the largest per-slot track (rollout_form goes by it)
+    // A fleet (mpopis_set_env_params_cars, multi-car handles): [B][num_cars] structs, allocated by the first call and moved
+    // with the slot views.  fleet_on excludes env_params_slots_on (each setter ends the other; mpopis_set_env_params ends both).  While it is in
+    // force the track array is passed as well (sync_slot_env fills it with copies of the shared descriptor when no per-slot tracks are set) and
+    // the per-slot car array is not: the rollout reads cars[] and track[], the small kernels cars[] behind a test of the pointer.
+    mpopis::CarParams* d_cars_sl = nullptr;
+    bool fleet_on = false;
     mpopis::SlotEnv slot_env() const {
         mpopis::SlotEnv se;
-        const bool car_any = env.kind == MPOPIS_ENV_CAR && (env_params_slots_on || track_slots_on);
-        if (env_params_slots_on || car_any) { se.car = d_car_sl; se.mc = d_mc_sl; se.cp = d_cp_sl; }
+        const bool car_any = env.kind == MPOPIS_ENV_CAR && (env_params_slots_on || track_slots_on || fleet_on);
+        if (env_params_slots_on || (car_any && !fleet_on)) { se.car = d_car_sl; se.mc = d_mc_sl; se.cp = d_cp_sl; }
         if (track_slots_on || car_any) { se.track = d_track_sl; se.lds_all = track_sl_lds_all; se.lds_ring = track_sl_lds_ring; }
+        if (fleet_on) se.cars = d_cars_sl;
         return se;
     }
     const mpopis::Track* slot_tracks() const { return slot_env().track; }

@@ -57,7 +57,7 @@ __global__ void k_harness_update(EnvDesc env, double* x, const int* done_env, co
             const double be = fabs(atan2(s[4], s[3]));
             vmean += v; bmean += be; vmax = fmax(vmax, v); bmax = fmax(bmax, be);
             d = fmin(d, sqrt(s[0] * s[0] + s[1] * s[1]));
-            if (be > env.car.blim) ex_b = true;
+            if (be > (senv.cars ? senv.cars[(size_t)b * NC + c].blim : env.car.blim)) ex_b = true;      // (a fleet: car c's own β limit)
             double dist;
             if (!within_track(env.track, s[0], s[1], &dist, nullptr)) within_t = false;
         }

@@ -207,6 +207,7 @@ __global__ void __launch_bounds__(64) k_env_step(EnvDesc env, double* x, int* t,
         if (NC == 1 && !(a0 >= env.lo[0] && a0 <= env.hi[0] && a1 >= env.lo[1] && a1 <= env.hi[1])) {
             if (status) status_raise(&status[b], MPOPIS_ERR_ACTION);                // car_racing.jl:239
         }
+        if (senv.cars) env.car = senv.cars[(size_t)b * NC + c];                    // a fleet: car c's own parameters
         CarState s;
         car_state_from8(s, xb + 8 * c);
         car_action_step(env.car, s, a0, a1);
@@ -251,6 +252,7 @@ __global__ void __launch_bounds__(64) k_env_query(EnvDesc env, const double* x, 
         if (!w) win = 0;
         if (dist) dist[(size_t)b * NC + i] = d;
         if (beta) beta[(size_t)b * NC + i] = atan2(s[4], s[3]);
+        if (senv.cars) env.car = senv.cars[(size_t)b * NC + i];                    // a fleet: car i's own parameters
         rew += car_reward(env.car, env.track, s[0], s[1], s[3], s[4]);
         for (int j = i + 1; j < NC; ++j) {
             const double dx = xb[8 * j] - s[0], dy = xb[8 * j + 1] - s[1];

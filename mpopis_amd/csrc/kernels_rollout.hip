@@ -21,6 +21,8 @@
 // kernels_rollout_slots.hip (it defines MPOPIS_ROLLOUT_SLOT_TWINS and includes this file): the kernel templates and the launcher templates are
 // shared, everything else -- the simple envs, the start-state kernels, rollout_form, launch_rollout -- exists here only.  The build stays as
 // long as its longest file that way; with both sets in one file it took twice the time.
+// A third unit, kernels_rollout_fleet.hip (one wave per car, for handles whose cars carry their own parameters), includes
+// this text with MPOPIS_ROLLOUT_FLEET as well and takes the pieces only: no kernel or launcher of this file is instantiated there.
 #include "engine.h"
 
 namespace mpopis {
@@ -548,7 +550,9 @@ static bool launch_car_rollout(const RolloutArgs& a, const RolloutForm& f, hipSt
     return true;
 }
 
-#ifdef MPOPIS_ROLLOUT_SLOT_TWINS
+#if defined(MPOPIS_ROLLOUT_FLEET)
+// (kernels_rollout_fleet.hip takes the pieces above and instantiates none of the kernels)
+#elif defined(MPOPIS_ROLLOUT_SLOT_TWINS)
 bool launch_car_rollout_slots(const RolloutArgs& a, const RolloutForm& f, hipStream_t st) { return launch_car_rollout(a, f, st); }
 #else
 // A caller's env (include/mpopis_env.h): the rollout kernel of its code object, same grid as k_rollout_simple.  The built-in kernels treat
@@ -604,6 +608,14 @@ RolloutForm rollout_form(const RolloutArgs& a) {
     f.tlds = lds_all <= kRolloutDynLdsDefault;      // (static LDS of the two-wave kernels counted: P = 221, 222 used to total 65.7-66 KB without the limit being raised)
     f.lds = f.tlds ? lds_all : a.senv.track ? a.senv.lds_ring : track_lds_bytes(P, W, false);
     if (NC < 1 || NC > kMaxCars) { f.body = ROLLOUT_ONE_WAVE_SPB1; return f; }           // (no kernel: launch_rollout returns false)
+    if (a.senv.cars) {
+        // A fleet: always the one-wave-per-car body, whose static LDS -- the position exchange, 16 KB at 8 cars -- counts
+        // against the default 64 KB where the placement is decided (the largest-track rule above holds: a fleet handle always passes senv.track)
+        f.body = ROLLOUT_FLEET;
+        f.tlds = lds_all + fleet_static_lds(NC) <= 64 * 1024;
+        f.lds = f.tlds ? lds_all : a.senv.track ? a.senv.lds_ring : track_lds_bytes(P, W, false);
+        return f;
+    }
     const int S = 64 / NC;
     const long long waves = (long long)a.B * ((a.K + S - 1) / S) * std::max(1, a.share);
     // (a per-slot-env handle takes the same body as a shared one: every instantiation has its twin)
@@ -621,6 +633,7 @@ bool launch_rollout(const RolloutArgs& a, hipStream_t st, hipError_t* custom_err
         hipLaunchKernelGGL(kernel, dim3((a.K + 63) / 64, a.B), dim3(64), 0, st, a);
         return true;
     }
+    if (f.body == ROLLOUT_FLEET) return launch_car_rollout_fleet(a, f, st);
     return a.senv.car && a.senv.track ? launch_car_rollout_slots(a, f, st) : launch_car_rollout(a, f, st);
 }
 #endif      // !MPOPIS_ROLLOUT_SLOT_TWINS

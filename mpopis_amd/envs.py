@@ -78,6 +78,8 @@ class _EnvBase:
         self._eng = Engine(self.kind, self.ncars, "gmppi", num_samples=1, horizon=1, batch=1, lam=1.0,
                            device=device, track=self.track.arrays() if self.kind == "car" else None,
                            env_params=self._param_vector(), custom_env=self if self.kind == "custom" else None)
+        if getattr(self, "car_fleet", None) is not None:            # MultiCarRacingEnv(N, car_params=[...]): every car its own vector
+            self._eng.set_env_params_cars(self.car_fleet)
         self._push()
 
     def _push(self):
@@ -132,10 +134,33 @@ class CarRacingEnv(_EnvBase):
             self._push()
 
 
+def fleet_from_car_params(N, car_params, dt, δt):
+    """The (N, 20) parameter vectors of MultiCarRacingEnv(N; car_params = [...]) (multi-car_racing.jl:35-45): entry i for car i + 1, defaults for the
+    cars past the list.  None for an empty list -- every car on the defaults, no fleet."""
+    car_params = list(car_params)
+    if len(car_params) > N:
+        raise MPOPISError(ERR_ARG, "# Car parameters must be ≤ # cars")          # :35
+    if not car_params:
+        return None
+    rows = []
+    for cp in car_params:
+        v = cp.vector(dt, δt) if isinstance(cp, CarRacingEnvParams) else _f64(cp).reshape(-1)
+        if v.size != 20:
+            raise MPOPISError(ERR_ARG, "car_params: each entry a CarRacingEnvParams or 20 values, got %d" % v.size)
+        rows.append(v)
+    rows += [CarRacingEnvParams().vector(dt, δt)] * (N - len(rows))
+    return np.stack(rows)
+
+
 class MultiCarRacingEnv(_EnvBase):
-    def __init__(self, N=2, dt=0.1, δt=0.01, track=None, rng=None, device=0):
+    """multi-car_racing.jl:23-58.  car_params: up to N parameter sets, one per car from car 1 on -- each a CarRacingEnvParams or the 20 values of
+    include/mpopis.h (dt and δt of a vector must be the env's) -- and the cars past the list get the defaults (:35-45).  With a non-empty list
+    the env is a FLEET: car_fleet holds the (N, 20) vectors and the engine steps, rewards and rolls out every car with its own."""
+
+    def __init__(self, N=2, dt=0.1, δt=0.01, track=None, rng=None, device=0, car_params=()):
         if not 1 <= N <= MAX_CARS:
             raise MPOPISError(ERR_ARG, "this engine supports 1..%d cars" % MAX_CARS)
+        self.car_fleet = fleet_from_car_params(N, car_params, dt, δt)
         self.N = N
         self.params = CarRacingEnvParams()
         self.dt, self.δt = dt, δt
@@ -355,4 +380,5 @@ def calculate_β(env):
 def exceed_β(env):
     if env.ncars == 1:
         return abs(calculate_β(env)) > env.params.β_limit         # :184-189
-    return any(abs(math.atan2(s[4], s[3])) > env.params.β_limit for s in env.envs)   # multi :130-136
+    lim = [env.params.β_limit] * env.N if getattr(env, "car_fleet", None) is None else env.car_fleet[:, 17]      # (a fleet: every car its own)
+    return any(abs(math.atan2(s[4], s[3])) > lim[i] for i, s in enumerate(env.envs))   # multi :130-136

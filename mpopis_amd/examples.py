@@ -140,6 +140,19 @@ def split_env_params_per_trial(value, n, num_trials, rank=0, world=1):
     return None, a[[k - 1 for k in shard_trials(num_trials, rank, world)]]
 
 
+def split_fleet_per_trial(value, num_cars, num_trials, rank=0, world=1):
+    """What one rank passes for `car_fleet` to Engine.set_env_params_cars (None: no fleet): (num_cars, 20) as it is -- every trial drives that
+    fleet --, or from (num_trials, num_cars, 20) the fleets of this rank's trials (shard_trials) in slot order."""
+    if value is None:
+        return None
+    a = np.asarray(value, dtype=np.float64)
+    if a.shape == (num_cars, 20):
+        return a
+    if a.shape != (num_trials, num_cars, 20):
+        raise ValueError("car_fleet: shape (num_cars, 20) = (%d, 20), or one fleet per trial (%d, %d, 20), got %s" % (num_cars, num_trials, num_cars, a.shape))
+    return a[[k - 1 for k in shard_trials(num_trials, rank, world)]]
+
+
 def _resolve_track(t):
     return default_track(name=t) if isinstance(t, str) else tuple(np.asarray(v, dtype=np.float64) for v in t)
 
@@ -156,7 +169,7 @@ def _apply_per_trial(eng, per, cov_slots, policy):
 def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="cemppi", laps=2, num_samples=150, horizon=50,
                         λ=10.0, α=1.0, U0=None, cov_mat=None, ais_its=10, λ_ais=20.0, ce_elite_threshold=0.8, ce_Σ_est="ss",
                         cma_σ=0.75, cma_elite_threshold=0.8, state_x_sigma=0.0, state_y_sigma=0.0, state_ψ_sigma=0.0,
-                        seed=None, log_runs=True, device=0, dist=None, quiet=False, track="curve", car_params=None, trace=None):
+                        seed=None, log_runs=True, device=0, dist=None, quiet=False, track="curve", car_params=None, trace=None, car_fleet=None):
     """Returns (records, summary) on rank 0 (None elsewhere).  Differences from the reference harness, all
     forced by the platform: plotting/GIF options are not offered (out of scope); the state noise (single car only,
     car_example.jl:224-236) is drawn from the trial's device stream instead of the env's MersenneTwister.
@@ -164,7 +177,8 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
     (split_per_trial): trial k runs with entry k - 1, all trials of a rank still in one resident batch -- a hyper-parameter sweep in one call.
     track: a bundled name (engine.BUNDLED_TRACKS) or an (x, y, w) triple, or a sequence of num_trials of either -- a policy over several tracks
     in one resident batch, every distinct track uploaded once (split_tracks_per_trial).  car_params: the 20 values of CarRacingEnvParams + dt, δt
-    (include/mpopis.h), or (num_trials, 20) for one vector per trial (split_env_params_per_trial).
+    (include/mpopis.h), or (num_trials, 20) for one vector per trial (split_env_params_per_trial).  car_fleet (num_cars > 1): one such vector per
+    CAR, (num_cars, 20) for every trial or (num_trials, num_cars, 20), sharded like car_params (split_fleet_per_trial); not together with car_params.
     ce_Σ_est defaults to :ss like the reference (car_example.jl:66); :mle is the other supported estimator.
     trace: as Engine.run_trials takes it (True, or dict(plan_every, top[, fields])) -- the run is recorded on the device, what plot_steps /
     save_gif / plot_traj of the reference draw, and the call returns (records, summary, trace) with the trace of THIS rank's trials in slot
@@ -187,7 +201,10 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
     λ, α, λ_ais, cma_σ = [v if split[k][1] is None else float(np.asarray(v, dtype=np.float64)[0]) for k, v in kw.items()]
     cov_shared, cov_slots = split_per_trial(cov_mat, num_trials, rank, world, cov=True)
     trk_shared, trk_slots = split_tracks_per_trial(track, num_trials, rank, world)
+    if car_params is not None and car_fleet is not None:
+        raise ValueError("car_params and car_fleet: give one of the two (one vector per slot, or one per car)")
     par_shared, par_slots = split_env_params_per_trial(car_params, 20, num_trials, rank, world)
+    fleet = split_fleet_per_trial(car_fleet, num_cars, num_trials, rank, world)
     t0 = time.time()
     # every rank keeps a handle (even with no trials: it takes part in the collective); all of a rank's trials
     # k0, k0+G, ... live in ONE resident batch, slot i seeded like the reference's trial k_i: seed!(pol, seed + k) (:187-188)
@@ -204,6 +221,8 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
             eng.set_tracks([_resolve_track(t) for t in trk_slots[0]], trk_slots[1])
         if par_slots is not None:
             eng.set_env_params_slots(par_slots)
+        if fleet is not None:
+            eng.set_env_params_cars(fleet)
         eng.seed_slots([seed + k for k in mine])
         eng.set_state_noise(state_x_sigma, state_y_sigma, state_ψ_sigma)
         if trace is None or trace is False:

@@ -52,6 +52,8 @@ class AbstractPathIntegralPolicy:
                            alpha=α, seed=seed, device=device, log_trajectories=log,
                            track=env.track.arrays() if env.kind == "car" else None, env_params=env._param_vector(),
                            cov=cov, U0=U0, custom_env=env if env.kind == "custom" else None, **extra)
+        if getattr(env, "car_fleet", None) is not None:             # MultiCarRacingEnv(N, car_params=[...]): the policy's model is the same fleet
+            self._eng.set_env_params_cars(env.car_fleet)
         p = _Params()
         p.num_samples, p.horizon, p.λ, p.α, p.U0 = num_samples, horizon, λ, α, U0
         p.ss, p.as_, p.cs, p.log = env.ss, as_, as_ * horizon, log
