@@ -79,7 +79,12 @@ extern "C" {
  *    Later gained ONE more entry point, mpopis_set_env_params_cars: one parameter vector per CAR of a multi-car slot, as every env.envs[i] of the
  *    reference's MultiCarRacingEnv owns its params (a heavy car beside a light one, worn tyres beside fresh ones).  mpopis_config and every other
  *    entry point are unchanged, and a handle that never calls it launches what it launched before; a library that predates it does not export
- *    the symbol, which is how a caller detects support (it gives every car of a slot the slot's one vector). */
+ *    the symbol, which is how a caller detects support (it gives every car of a slot the slot's one vector).
+ *    Later gained THREE more entry points, mpopis_set_noise_kind, mpopis_get_noise_kind and mpopis_draw_normals, and the enum MPOPIS_NOISE_*: the
+ *    proposal's standard normals drawn on the device by antithetic pairs or Latin-hypercube strata instead of plain Philox / Box-Muller, and a
+ *    read-out of the normals the handle draws.  mpopis_config and every other entry point are unchanged, and a handle that never leaves
+ *    MPOPIS_NOISE_PHILOX (or returns to it) launches what it launched before, bit for bit; a library that predates them does not export the
+ *    symbols, which is how a caller detects support. */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -270,6 +275,34 @@ int  mpopis_seed(mpopis_handle *h, uint64_t seed);                          /* s
  * src/examples/car_example.jl:187-188; a rank that holds the trials k0, k0+G, k0+2G, ... of a sharded run
  *  passes {seed + k0, seed + k0 + G, ...} so that all of them stay in ONE resident batch. */
 int  mpopis_seed_slots(mpopis_handle *h, const uint64_t *seeds /* B */);
+/* How the handle draws the proposal's standard normals on the device, i.e. wherever noise == NULL: mpopis_policy_step, mpopis_policy_call,
+ * mpopis_run_trials, mpopis_run_trials_traced and mpopis_bench_policy_steps, for every policy (:mppi included) and every env kind.  One kind per
+ * handle.  Injected noise is consumed as it is; the resampling draws of :pmcmppi and the state noise stay Philox draws.
+ * Per slot b, Z row r (r = t*as + a in both layouts of mpopis_noise.Z), sample k, MPC step and AIS iteration n:
+ *   MPOPIS_NOISE_PHILOX      (default) Z = randn from the slot's Philox4x32-10 stream (step, n) and Box-Muller
+ *   MPOPIS_NOISE_ANTITHETIC  with h = ceil(K/2): column k < h is, bit for bit, the MPOPIS_NOISE_PHILOX normal of (r, k); column k >= h is the exact
+ *                            negation of column k - h (odd K: column h - 1 has no partner)
+ *   MPOPIS_NOISE_LHS         Latin hypercube: sample k of row r falls in stratum j = pi_r(k), a keyed bijection of [0, K) evaluated per element
+ *                            (four Feistel rounds over the even number of bits that covers K, cycle walking; round keys = Philox words of
+ *                            (seed, step, n, r)); Z = Phi^-1((j + xi) / K) with the jitter xi = (x + 0.5) 2^-32 from a Philox word x of
+ *                            (seed, step, n, r, k).  Stratum j with jitter xi and stratum K - 1 - j with jitter 1 - xi give exact negatives.
+ *                            K <= 2^20 (MPOPIS_ERR_ARG beyond).
+ * The new kinds always draw plain standard normals into memory and scale / unwhiten them with the kernels an injected step runs, so a device step
+ * and a step with the same normals injected compute the same bits; results do not depend on the schedule (mpopis_set_overlap).
+ *   mpopis_set_noise_kind  a setup call like mpopis_set_slot_hyper: it waits for everything the handle has queued; a refused call (an unknown
+ *                          kind, MPOPIS_NOISE_LHS with K > 2^20: MPOPIS_ERR_ARG) leaves the handle as it was.  After a return to
+ *                          MPOPIS_NOISE_PHILOX the handle's results are those of a handle that never switched.
+ *   mpopis_get_noise_kind  the kind in force
+ *   mpopis_draw_normals    the standard normals the handle would draw for MPC step mpc_step and AIS iteration `iteration` (0-based) under its current
+ *                          kind and slot seeds, all three kinds, every slot: Z is B x (cs x K col-major) -- one iteration of mpopis_noise.Z --,
+ *                          for :mppi B x (K*T*as), element ((t*K+k)*as+a).  A policy step given these as injected noise reproduces the device
+ *                          step of the new kinds bit for bit (under MPOPIS_NOISE_PHILOX to rounding: dense shapes draw inside the unwhitening kernel).
+ *                          A getter: it advances no RNG position, writes nothing a later call reads and keeps the source of mpopis_get_plan.
+ *                          MPOPIS_ERR_ARG: NULL Z, a negative iteration; MPOPIS_ERR_HIP when its B*cs*K-double staging buffers cannot be allocated. */
+enum { MPOPIS_NOISE_PHILOX = 0, MPOPIS_NOISE_ANTITHETIC = 1, MPOPIS_NOISE_LHS = 2 };
+int  mpopis_set_noise_kind(mpopis_handle *h, int32_t kind);
+int  mpopis_get_noise_kind(mpopis_handle *h, int32_t *kind);
+int  mpopis_draw_normals(mpopis_handle *h, uint32_t mpc_step, int32_t iteration /* 0-based */, double *Z);
 /* Σ′ of the proposal MvNormal the LAST executed AIS iteration of the last policy step drew from, per slot:
  * B x (cs x cs col-major).  (:447,:723,:796 `P = MvNormal(Σ′)`; :cmamppi with N > 1: σ²·Σ′, :550-554; policies
  * that keep pol.Σ fixed return pol.Σ; :nesmppi: A′'A′ of the last executed iteration, pol.Σ when the call broke at n = 1.)  Lets a caller compare the adapted covariance, which the reference
@@ -338,7 +371,7 @@ int  mpopis_get_trajectories(mpopis_handle *h, double *out);
  * "after the final shift" that mpopis_policy_step returns, so a caller can reproduce every rollout from U_orig and E_out.
  * Source and validity: the call reads the last successful mpopis_policy_step / mpopis_policy_call of the handle, which stays readable only
  * until another call writes to the handle.  The getters keep it: mpopis_get_state, mpopis_get_U, mpopis_get_Sigma, mpopis_get_slot_hyper,
- * mpopis_get_trajectories, mpopis_env_query, mpopis_last_error, mpopis_timing_read and mpopis_get_plan itself.  EVERY other entry point ends it
+ * mpopis_get_trajectories, mpopis_env_query, mpopis_last_error, mpopis_timing_read, mpopis_get_noise_kind, mpopis_draw_normals and mpopis_get_plan itself.  EVERY other entry point ends it
  * (mpopis_env_step, mpopis_set_state, mpopis_set_U, mpopis_reset, mpopis_rollout_costs, mpopis_run_trials, mpopis_bench_policy_steps, every
  * setter, the timing switches, the communicator calls), and so does a step that returned an error.  Without a valid source the call returns
  * MPOPIS_ERR_ARG and mpopis_last_error says which of the three applies: no step yet, the last step failed, or which call wrote.

@@ -33,7 +33,18 @@ ABI_SYMBOLS = [
     "mpopis_create_custom", "mpopis_set_env_table", "mpopis_policy_call", "mpopis_set_overlap", "mpopis_comm_unique_id", "mpopis_comm_init", "mpopis_gather_summary", "mpopis_comm_destroy", "mpopis_comm_count",
     "mpopis_set_slot_hyper", "mpopis_get_slot_hyper", "mpopis_set_Sigma_slots", "mpopis_set_env_params_slots", "mpopis_set_tracks",
     "mpopis_get_plan", "mpopis_run_trials_traced", "mpopis_set_env_params_cars",
+    "mpopis_set_noise_kind", "mpopis_get_noise_kind", "mpopis_draw_normals",
 ]
+# MPOPIS_NOISE_*: how the device draws the proposal's standard normals (mpopis_set_noise_kind)
+NOISE_IDS = {"philox": 0, "antithetic": 1, "lhs": 2}
+
+
+def noise_id(kind):
+    """"philox" | "antithetic" | "lhs" (a leading ':' is ignored) -> MPOPIS_NOISE_*; anything else is refused here, before the library is reached"""
+    k = str(kind).lstrip(":")
+    if k not in NOISE_IDS:
+        raise MPOPISError(ERR_ARG, "unknown noise kind %r (philox, antithetic, lhs)" % (kind,))
+    return NOISE_IDS[k]
 
 
 class Config(C.Structure):
@@ -98,6 +109,10 @@ def lib():
             L.mpopis_run_trials_traced.argtypes = [H, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(Trace)]
         if hasattr(L, "mpopis_set_env_params_cars"):            # (one parameter vector per car of a multi-car slot)
             L.mpopis_set_env_params_cars.argtypes = [H, _dp, C.c_int32, C.c_int32]
+        if hasattr(L, "mpopis_set_noise_kind"):                 # (antithetic / Latin-hypercube draws and the read-out of the device's normals)
+            L.mpopis_set_noise_kind.argtypes = [H, C.c_int32]
+            L.mpopis_get_noise_kind.argtypes = [H, _ip]
+            L.mpopis_draw_normals.argtypes = [H, C.c_uint32, C.c_int32, _dp]
         L.mpopis_destroy.argtypes = [H]
         L.mpopis_destroy.restype = None
         L.mpopis_set_env_params.argtypes = [H, _dp, C.c_int32]

@@ -234,6 +234,11 @@ SampleNormalForm sample_normal_form(int cs, int as, int mppi_order);
 void launch_rng_tab_init(double* gtab, hipStream_t s);      // philox.h: kRngTabDoubles doubles (Box-Muller tables), once per handle
 void launch_sample_resample_draws(int32_t* di, double* du, int B, int K, const uint64_t* seeds, uint32_t slo, uint32_t shi,
                                   const int* active, hipStream_t s);
+// kernels_strat.hip: Z[b][r][k] = plain standard normals of the antithetic (kind MPOPIS_NOISE_ANTITHETIC) or Latin-hypercube (MPOPIS_NOISE_LHS,
+// K <= 2^20) draw of (seed, step, iter); both orders; rows of inactive slots are not written
+constexpr int kStratMaxK = 1 << 20;
+void launch_sample_strat(double* Z, int B, int cs, int K, int as, int mppi_order, int kind, const uint64_t* seeds, uint32_t step, uint32_t iter,
+                         const int* active, hipStream_t s, const double* rng_tab);
 
 
 // Workspace of the cooperative ("cluster") kernels: several workgroups per matrix that exchange through global memory and therefore need

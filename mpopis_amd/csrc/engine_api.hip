@@ -912,6 +912,52 @@ int mpopis_seed_slots(mpopis_handle* h, const uint64_t* seeds) {
     return MPOPIS_OK;
 }
 
+// How the device draws the proposal's normals.  A setup call: the kind is read while a step is enqueued, never by a kernel,
+// but the call still waits for what is queued so that it orders like the other setters.
+int mpopis_set_noise_kind(mpopis_handle* h, int32_t kind) {
+    if (h) h->plan_drop("mpopis_set_noise_kind");
+    if (!h) return MPOPIS_ERR_ARG;
+    if (kind != MPOPIS_NOISE_PHILOX && kind != MPOPIS_NOISE_ANTITHETIC && kind != MPOPIS_NOISE_LHS) {
+        h->err = "mpopis_set_noise_kind: unknown noise kind " + std::to_string(kind) + " (0 philox, 1 antithetic, 2 lhs)"; return MPOPIS_ERR_ARG;
+    }
+    if (kind == MPOPIS_NOISE_LHS && h->K > kStratMaxK) { h->err = "mpopis_set_noise_kind: the Latin-hypercube draw takes K <= 2^20"; return MPOPIS_ERR_ARG; }
+    if (const int rc = quiesce(h)) return rc;
+    h->noise_kind = kind;
+    return MPOPIS_OK;
+}
+
+int mpopis_get_noise_kind(mpopis_handle* h, int32_t* kind) {
+    if (!h || !kind) return MPOPIS_ERR_ARG;
+    *kind = h->noise_kind;
+    return MPOPIS_OK;
+}
+
+// The normals of (mpc_step, iteration) under the handle's kind and seeds, in the layout of one iteration of mpopis_noise.Z.  Drawn into staging
+// buffers of the call's own (allocated and freed here), so nothing a later call reads is written and the RNG position (mpc_step) stays.
+int mpopis_draw_normals(mpopis_handle* h, uint32_t mpc_step, int32_t iteration, double* Z) {
+    if (!h) return MPOPIS_ERR_ARG;
+    if (!Z || iteration < 0) { h->err = "mpopis_draw_normals: Z must not be NULL and iteration must be >= 0"; return MPOPIS_ERR_ARG; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int B = h->B, K = h->K, cs = h->cs, as = h->as;
+    const bool mppi = h->cfg.policy == MPOPIS_POL_MPPI;
+    const size_t n = (size_t)B * cs * K;
+    double* rows = nullptr; double* out = nullptr;
+    if (hipMalloc((void**)&rows, sizeof(double) * n) != hipSuccess || hipMalloc((void**)&out, sizeof(double) * n) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(rows);
+        h->err = "mpopis_draw_normals: hipMalloc of the staging buffers failed"; return MPOPIS_ERR_HIP;
+    }
+    if (h->noise_kind == MPOPIS_NOISE_PHILOX) launch_sample_normal(rows, B, cs, K, as, mppi, h->d_seeds, mpc_step, (uint32_t)iteration, nullptr, nullptr, h->stream, h->d_rng_tab);
+    else launch_sample_strat(rows, B, cs, K, as, mppi, h->noise_kind, h->d_seeds, mpc_step, (uint32_t)iteration, nullptr, h->stream, h->d_rng_tab);
+    if (mppi) launch_mppi_E_out(rows, out, B, h->T, K, as, h->stream);
+    else launch_transpose_out(rows, nullptr, nullptr, out, B, cs, K, h->stream);
+    hipError_t e = hipMemcpyAsync(Z, out, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = wait_stream(h->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    (void)hipFree(rows); (void)hipFree(out);
+    HIPCHK(h, e);
+    return MPOPIS_OK;
+}
+
 int mpopis_get_Sigma(mpopis_handle* h, double* out) {
     if (!h || !out) return MPOPIS_ERR_ARG;
     if (h->cfg.policy == MPOPIS_POL_MPPI) { h->err = "mpopis_get_Sigma: :mppi keeps the as x as pol.Σ (no adaptation)"; return MPOPIS_ERR_ARG; }
@@ -1530,7 +1576,9 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
     static const int env_zpre = [] { const char* e = getenv("MPOPIS_ZPREFETCH"); return e ? atoi(e) : 1; }();
     // (the fork and the wait are two packets of ~6 us each on the main stream: below ~4 M normals per draw -- one or two C4 trials, an 8-12 us kernel -- drawing in line is
     // shorter: 4.20 -> 4.165 ms per C4 step at one trial, 4.55 -> 4.525 at two, neutral at four, +1 % at eight)
-    const bool z_prefetch_ok = env_zpre && (env_zpre == 2 || (!sample_trmm_fusable(cs) && (size_t)B * cs * K >= (size_t)4000000)) && side_free && xstream[1] && !injected &&
+    // (the antithetic and Latin-hypercube draws are generated in line: no prefetch, no fused form -- they end in the kernels an injected step runs)
+    const bool strat = !injected && noise_kind != MPOPIS_NOISE_PHILOX;
+    const bool z_prefetch_ok = env_zpre && (env_zpre == 2 || (!sample_trmm_fusable(cs) && (size_t)B * cs * K >= (size_t)4000000)) && side_free && xstream[1] && !injected && !strat &&
                                pol != MPOPIS_POL_MPPI && pol != MPOPIS_POL_PMCMPPI /* d_Z holds E[:, idx] there */ && !(sigma_diag && sigma_fixed) && N > 1;
     bool z_prefetched = false;
     for (int n = 1; n <= N; ++n) {
@@ -1563,6 +1611,9 @@ int mpopis_handle::step_enqueue_view(bool injected, hipEvent_t wait_first, hipEv
             // B x N x (cs x K col-major) -> rows; source slot stride N*per
             if (pol == MPOPIS_POL_MPPI) launch_mppi_Z_in(d_Zin, Zdst, B, T, K, as, stream);       // N == 1
             else launch_transpose_in(d_Zin + (size_t)(n - 1) * per, Zdst, B, cs, K, stream, (size_t)N * per);
+            if (dsc) launch_scale_rows(Zdst, dsc, B, cs, K, stream);
+        } else if (strat) {
+            launch_sample_strat(Zdst, B, cs, K, as, pol == MPOPIS_POL_MPPI, noise_kind, d_seeds, (uint32_t)mpc_step, (uint32_t)(n - 1), d_active, stream, d_rng_tab);
             if (dsc) launch_scale_rows(Zdst, dsc, B, cs, K, stream);
         } else if (z_prefetched) {
             // this iteration's standard normals were drawn on the side stream while the previous iteration's reweighting / moments / Cholesky

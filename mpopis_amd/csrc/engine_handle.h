@@ -115,6 +115,7 @@ struct mpopis_handle {
     unsigned long long* d_iters_acc = nullptr;   // per slot: AIS iterations executed by the policy steps BEFORE the last one (k_step_begin folds iters in before clearing it)
     uint64_t* d_seeds = nullptr;
     double* d_rng_tab = nullptr;            // Box-Muller tables (philox.h), filled at creation
+    int noise_kind = MPOPIS_NOISE_PHILOX;   // how the device draws the proposal's normals (mpopis_set_noise_kind)
     // elite selection / resampling
     int32_t *d_order = nullptr, *d_resi = nullptr, *d_alias = nullptr, *d_residx_log = nullptr, *d_resi_in = nullptr;
     double *d_resu = nullptr, *d_accept = nullptr, *d_resu_in = nullptr;

@@ -9,7 +9,7 @@ import warnings
 import numpy as np
 
 from .engine import Engine, default_track
-from ._lib import MPOPISError, ERR_ARG, RECORD_LEN
+from ._lib import MPOPISError, ERR_ARG, RECORD_LEN, noise_id
 
 
 def quantile_ci(x, p=0.05, q=0.5):
@@ -169,7 +169,7 @@ def _apply_per_trial(eng, per, cov_slots, policy):
 def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="cemppi", laps=2, num_samples=150, horizon=50,
                         λ=10.0, α=1.0, U0=None, cov_mat=None, ais_its=10, λ_ais=20.0, ce_elite_threshold=0.8, ce_Σ_est="ss",
                         cma_σ=0.75, cma_elite_threshold=0.8, state_x_sigma=0.0, state_y_sigma=0.0, state_ψ_sigma=0.0,
-                        seed=None, log_runs=True, device=0, dist=None, quiet=False, track="curve", car_params=None, trace=None, car_fleet=None):
+                        seed=None, log_runs=True, device=0, dist=None, quiet=False, track="curve", car_params=None, trace=None, car_fleet=None, noise="philox"):
     """Returns (records, summary) on rank 0 (None elsewhere).  Differences from the reference harness, all
     forced by the platform: plotting/GIF options are not offered (out of scope); the state noise (single car only,
     car_example.jl:224-236) is drawn from the trial's device stream instead of the env's MersenneTwister.
@@ -182,8 +182,10 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
     ce_Σ_est defaults to :ss like the reference (car_example.jl:66); :mle is the other supported estimator.
     trace: as Engine.run_trials takes it (True, or dict(plan_every, top[, fields])) -- the run is recorded on the device, what plot_steps /
     save_gif / plot_traj of the reference draw, and the call returns (records, summary, trace) with the trace of THIS rank's trials in slot
-    order (trial ids: shard_trials; traces are not gathered; an empty dict on a rank without trials)."""
+    order (trial ids: shard_trials; traces are not gathered; an empty dict on a rank without trials).
+    noise: how every trial draws its proposal's normals -- "philox" (default), "antithetic" or "lhs" (Engine.set_noise_kind); one kind per call."""
     pt = str(policy_type).lstrip(":")
+    noise_id(noise)                                    # (an unknown kind is refused before the library is reached)
     rank = dist.get_rank() if (dist is not None and dist.is_initialized()) else 0
     world = dist.get_world_size() if (dist is not None and dist.is_initialized()) else 1
     if seed is None:
@@ -224,6 +226,8 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
         if fleet is not None:
             eng.set_env_params_cars(fleet)
         eng.seed_slots([seed + k for k in mine])
+        if noise_id(noise) != 0:
+            eng.set_noise_kind(noise)
         eng.set_state_noise(state_x_sigma, state_y_sigma, state_ψ_sigma)
         if trace is None or trace is False:
             r = eng.run_trials(num_steps, laps)
@@ -267,8 +271,9 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
 
 def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cemppi", num_samples=20, horizon=15, λ=0.1, α=1.0, U0=(0.0,),
                          cov_mat=(1.5,), ais_its=5, λ_ais=0.1, ce_elite_threshold=0.8, ce_Σ_est="mle", cma_σ=0.75,
-                         cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None):
+                         cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None, noise="philox"):
     pt = str(policy_type).lstrip(":")
+    noise_id(noise)                                    # (an unknown kind is refused before the library is reached)
     par_shared, par_slots = split_env_params_per_trial(env_params, 11 if env_kind == "cartpole" else 8, num_trials)
     if seed is None:
         seed = int(np.random.default_rng().integers(1, 10 ** 10))
@@ -285,6 +290,8 @@ def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cem
         eng.set_env_params_slots(par_slots)
     if x0 is not None:
         eng.set_state(np.asarray(x0, dtype=np.float64).reshape(num_trials, ss))
+    if noise_id(noise) != 0:
+        eng.set_noise_kind(noise)
     t0 = time.time()
     traced = not (trace is None or trace is False)
     rec, tr_out = eng.run_trials(num_steps, 0, trace=trace) if traced else (eng.run_trials(num_steps, 0), None)
@@ -304,13 +311,14 @@ def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cem
 
 _SIMPLE_KW = dict(num_trials=1, num_steps=200, policy_type="cemppi", num_samples=20, horizon=15, λ=0.1, α=1.0, U0=(0.0,),
                   cov_mat=(1.5,), ais_its=5, λ_ais=0.1, ce_elite_threshold=0.8, ce_Σ_est="mle", cma_σ=0.75,
-                  cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None)
+                  cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None, noise="philox")
 
 
 def simulate_mountaincar(**kw):
     """mountaincar_example.jl:49-207 (same keyword arguments and defaults); x0: per-trial start positions
     (the reference draws x ~ U(-0.6,-0.4) from an unseeded RNG; default here -0.5).  env_params: the 8 values include/mpopis.h lists for
-    MountainCar, or (num_trials, 8) for one vector per trial.  trace: as simulate_car_racing; the call then returns (records, summary, trace)."""
+    MountainCar, or (num_trials, 8) for one vector per trial.  trace: as simulate_car_racing; the call then returns (records, summary, trace).
+    noise: "philox" (default), "antithetic" or "lhs", as simulate_car_racing."""
     a = dict(_SIMPLE_KW); _check_kw(a, kw); a.update(kw)
     if a["x0"] is not None:
         x = np.asarray(a["x0"], dtype=np.float64).reshape(a["num_trials"])
@@ -322,7 +330,8 @@ def simulate_cartpole(**kw):
     """cartpole_example.jl:8-190 (same keyword arguments and defaults); x0: (num_trials, 4) start states
     [x, xdot, theta, thetadot].  The reference draws 0.1*rand(4) - 0.05 from an unseeded MersenneTwister (:111);
     default here: the same box drawn from numpy's default_rng(seed + k).  env_params: the 11 values include/mpopis.h lists for CartPole, or
-    (num_trials, 11) for one vector per trial.  trace: as simulate_car_racing; the call then returns (records, summary, trace)."""
+    (num_trials, 11) for one vector per trial.  trace: as simulate_car_racing; the call then returns (records, summary, trace).
+    noise: "philox" (default), "antithetic" or "lhs", as simulate_car_racing."""
     a = dict(_SIMPLE_KW); _check_kw(a, kw); a.update(kw)
     if a["seed"] is None:
         a["seed"] = int(np.random.default_rng().integers(1, 10 ** 10))

@@ -74,6 +74,15 @@ class AbstractPathIntegralPolicy:
     def U(self, v):
         self._eng.set_U(_f64(v)[None])
 
+    @property
+    def noise_kind(self):
+        """How pol(env) draws its standard normals on the device: "philox" (default), "antithetic" or "lhs" (Engine.set_noise_kind)."""
+        return self._eng.noise_kind
+
+    @noise_kind.setter
+    def noise_kind(self, kind):
+        self._eng.set_noise_kind(kind)
+
     def seed(self, seed):
         """Random.seed!(pol, seed): src/MPOPIS.jl:54"""
         self._eng.seed(int(seed) - 1)          # slot 0 draws from seed+0+1
