@@ -93,6 +93,16 @@ struct SlotEnv {
     const CarParams* cars = nullptr;
     bool any() const { return car || mc || cp || track || cars; }
 };
+// lds_all / lds_ring of a SlotEnv from the HOST copy of its [n] track descriptors (mpopis_set_tracks; tools/kbench_rollout.hip forms its SlotEnv
+// through this too, so a harness launch gets the LDS size a handle's launch gets)
+inline void slot_tracks_lds(const Track* host, size_t n, size_t* lds_all, size_t* lds_ring) {
+    size_t all = 0, ring = 0;
+    for (size_t b = 0; b < n; ++b) {
+        const size_t a = track_lds_bytes(host[b].P, host[b].nbrw, true), r = track_lds_bytes(host[b].P, host[b].nbrw, false);
+        all = a > all ? a : all; ring = r > ring ? r : ring;
+    }
+    *lds_all = all; *lds_ring = ring;
+}
 // the small kernels (env step / query, harness bookkeeping, the simple envs' rollout) overwrite their by-value EnvDesc with slot b's parts
 __device__ __forceinline__ void slot_env_into(EnvDesc& env, const SlotEnv& se, int b) {
     if (se.car) env.car = se.car[b];

@@ -650,11 +650,8 @@ int mpopis_set_tracks(mpopis_handle* h, int32_t ntracks, const int32_t* P, const
         off += (size_t)P[i];
     }
     std::vector<Track> host((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        host[b] = tks[track_of_slot ? track_of_slot[b] : b];
-        lds_all = std::max(lds_all, track_lds_bytes(host[b].P, host[b].nbrw, true));
-        lds_ring = std::max(lds_ring, track_lds_bytes(host[b].P, host[b].nbrw, false));
-    }
+    for (int b = 0; b < B; ++b) host[b] = tks[track_of_slot ? track_of_slot[b] : b];
+    slot_tracks_lds(host.data(), host.size(), &lds_all, &lds_ring);
     // both arrays are allocated before either is written: past this point nothing can fail but a copy on a quiesced stream
     if (h->slot_alloc(h->d_track_sl, 1) || h->slot_alloc(h->d_car_sl, 1)) { (void)hipGetLastError(); h->err = "mpopis_set_tracks: hipMalloc of the per-slot env arrays failed"; return MPOPIS_ERR_HIP; }
     HIPCHK(h, hipMemcpyAsync(h->d_track_sl, host.data(), sizeof(Track) * B, hipMemcpyHostToDevice, h->stream));
