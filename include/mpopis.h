@@ -84,7 +84,12 @@ extern "C" {
  *    proposal's standard normals drawn on the device by antithetic pairs or Latin-hypercube strata instead of plain Philox / Box-Muller, and a
  *    read-out of the normals the handle draws.  mpopis_config and every other entry point are unchanged, and a handle that never leaves
  *    MPOPIS_NOISE_PHILOX (or returns to it) launches what it launched before, bit for bit; a library that predates them does not export the
- *    symbols, which is how a caller detects support. */
+ *    symbols, which is how a caller detects support.
+ *    Later gained FOUR more entry points, mpopis_set_scenarios, mpopis_set_risk, mpopis_get_scenarios and mpopis_get_scenario_costs, and the enum
+ *    MPOPIS_RISK_*: every rollout of a policy step scored under up to 16 model parameter vectors that need not be the plant's, the K costs the
+ *    step sees being a risk aggregate (mean, worst case, tail mean / CVaR, entropic) of the per-model costs.  mpopis_config and every other entry
+ *    point are unchanged, and a handle that never calls mpopis_set_scenarios (or ends the mode with M = 0) launches what it launched before, bit
+ *    for bit; a library that predates them does not export the symbols, which is how a caller detects support. */
 #define MPOPIS_ABI_VERSION 5
 
 enum { MPOPIS_OK = 0, MPOPIS_ERR_ARG = -1, MPOPIS_ERR_NOT_PD = -2, MPOPIS_ERR_ACTION = -3, MPOPIS_ERR_HIP = -4, MPOPIS_ERR_NUMERIC = -5 };
@@ -237,6 +242,38 @@ int  mpopis_set_tracks(mpopis_handle *h, int32_t ntracks, const int32_t *P, cons
  * refused or failed call leaves the handle as it was).  MPOPIS_ERR_ARG: another env kind, a custom handle, n != 20, NULL p, dt or δt that
  * differ inside a slot (mpopis_last_error names the slot and the car). */
 int  mpopis_set_env_params_cars(mpopis_handle *h, const double *p /* [B*]num_cars*n */, int32_t n /* 20 */, int32_t per_slot);
+/* Scenarios: score every rollout of a policy step under M model parameter vectors and hand the step a risk aggregate.
+ *   mpopis_set_scenarios  M = 1..MPOPIS_MAX_SCENARIOS vectors of n doubles (n as for mpopis_set_env_params_slots; all cars of a multi-car slot share
+ *     the scenario's vector).  per_slot == 0: p holds M*n doubles for every slot; otherwise B*M*n, slot b / scenario m at p[(b*M+m)*n].  From then on
+ *     every rollout of a policy step of slot b (mpopis_policy_step, mpopis_policy_call, mpopis_rollout_costs, mpopis_run_trials[_traced],
+ *     mpopis_bench_policy_steps) runs once per scenario -- same start state, pol.U, noise and control cost -- and the K costs the rest of the step
+ *     sees (weights, elite sort, resampling, moments, the `cost` outputs, the non-finite check) are the aggregate J of the M scenario costs of each
+ *     sample.  Nothing else of any policy changes.  THE REAL ENV IS UNTOUCHED: mpopis_env_step, mpopis_env_query, mpopis_reset, the bookkeeping of
+ *     mpopis_run_trials and the state noise keep the handle's own parameters (shared or per slot), and mpopis_set_env_params[_slots] after this call
+ *     change the plant only -- M = 1 is "model != plant".  Scenario 0 is the nominal model: the rollouts of mpopis_get_plan and of the trace's
+ *     plans run under it.  M = 0 (p may be NULL) ends the mode: results are then again, bit for bit, those of a handle that never had scenarios.
+ *     A setup call like mpopis_set_env_params_slots (waits for what is queued, allocates at the first call and when M grows -- MPOPIS_ERR_HIP when
+ *     that fails --, a refused call leaves the handle as it was).  It resets the risk to the mean (MPOPIS_RISK_TAIL_MEAN, tail = M).
+ *     MPOPIS_ERR_ARG: M outside 0..16, a wrong n, NULL p with M > 0, a custom handle, a handle created with log_trajectories (the logger has one
+ *     trajectory per sample), a fleet handle (mpopis_set_env_params_cars in force).  mpopis_set_env_params_cars on a scenario handle is refused too.
+ *   mpopis_set_risk  with the scenario costs c_0..c_{M-1} of one sample:
+ *     MPOPIS_RISK_TAIL_MEAN, tail in 1..M (0 means M): J = the mean of the `tail` largest costs, summed from the largest down.  tail = M is the
+ *       expectation, tail = 1 the worst case (the bits of that input), tail = ceil(qM) the discrete CVaR_q.  Any NaN among the c_m gives NaN;
+ *       otherwise plain IEEE arithmetic (an infinity takes part in the sort and the sum).
+ *     MPOPIS_RISK_ENTROPIC, finite theta != 0: J = c* + (1/theta) log((1/M) sum_m exp(theta (c_m - c*))), c* = max c_m for theta > 0 (risk-averse),
+ *       min c_m for theta < 0.  If any c_m is not finite, J is the IEEE sum of the non-finite c_m: NaN if one is NaN or both infinities occur,
+ *       else that infinity.
+ *     A non-finite J raises MPOPIS_ERR_ACTION in the slot's status where a non-finite rollout cost does.
+ *     MPOPIS_ERR_ARG: no scenarios set, an unknown kind, tail outside 0..M, theta zero or non-finite (MPOPIS_RISK_ENTROPIC).
+ *   mpopis_get_scenarios  M (0: off), kind, tail (as resolved: 1..M) and theta in force; any pointer may be NULL.
+ *   mpopis_get_scenario_costs  out[(b*M+m)*K+k]: the scenario costs behind the slot's current `cost`, i.e. of the last rollout the slot executed
+ *     (slots that broke early keep those of their last iteration).  A getter like mpopis_draw_normals.  MPOPIS_ERR_ARG without scenarios. */
+#define MPOPIS_MAX_SCENARIOS 16
+enum { MPOPIS_RISK_TAIL_MEAN = 0, MPOPIS_RISK_ENTROPIC = 1 };
+int  mpopis_set_scenarios(mpopis_handle *h, int32_t M, const double *p /* [B*]M*n */, int32_t n, int32_t per_slot);
+int  mpopis_set_risk(mpopis_handle *h, int32_t kind, int32_t tail, double theta);
+int  mpopis_get_scenarios(mpopis_handle *h, int32_t *M, int32_t *kind, int32_t *tail, double *theta);
+int  mpopis_get_scenario_costs(mpopis_handle *h, double *out /* B*M*K */);
 int  mpopis_set_action_bounds(mpopis_handle *h, const double *lo, const double *hi); /* action_space(env) */
 int  mpopis_reset(mpopis_handle *h);                       /* reset!(env) per slot: car_racing.jl:215-223, multi :160-180 */
 int  mpopis_set_state(mpopis_handle *h, const double *x /* B*ss */, const int32_t *t, const int32_t *done);
@@ -371,7 +408,7 @@ int  mpopis_get_trajectories(mpopis_handle *h, double *out);
  * "after the final shift" that mpopis_policy_step returns, so a caller can reproduce every rollout from U_orig and E_out.
  * Source and validity: the call reads the last successful mpopis_policy_step / mpopis_policy_call of the handle, which stays readable only
  * until another call writes to the handle.  The getters keep it: mpopis_get_state, mpopis_get_U, mpopis_get_Sigma, mpopis_get_slot_hyper,
- * mpopis_get_trajectories, mpopis_env_query, mpopis_last_error, mpopis_timing_read, mpopis_get_noise_kind, mpopis_draw_normals and mpopis_get_plan itself.  EVERY other entry point ends it
+ * mpopis_get_trajectories, mpopis_env_query, mpopis_last_error, mpopis_timing_read, mpopis_get_noise_kind, mpopis_draw_normals, mpopis_get_scenarios, mpopis_get_scenario_costs and mpopis_get_plan itself.  EVERY other entry point ends it
  * (mpopis_env_step, mpopis_set_state, mpopis_set_U, mpopis_reset, mpopis_rollout_costs, mpopis_run_trials, mpopis_bench_policy_steps, every
  * setter, the timing switches, the communicator calls), and so does a step that returned an error.  Without a valid source the call returns
  * MPOPIS_ERR_ARG and mpopis_last_error says which of the three applies: no step yet, the last step failed, or which call wrote.

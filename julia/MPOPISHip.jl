@@ -193,4 +193,27 @@ function MPOPIS.seed!(pol::BoundPolicy, seed::Integer)
     pol
 end
 
+# ---- scenarios and risk (include/mpopis.h: mpopis_set_scenarios / mpopis_set_risk) ----------------------------
+# set_scenarios!(pol, env, P): plan against the M model parameter vectors in the columns of P (n x M: the vector the handle of `env` takes, one
+# column per scenario) while `env` itself stays the plant; an empty P ends it.  set_risk!(pol, env, kind; tail, θ): :mean, :worst, :cvar (the
+# mean of the `tail` largest scenario costs) or :entropic (θ ≠ 0, θ > 0 risk-averse).  A library that predates the symbols fails here, loudly.
+const RISK_TAIL_MEAN = 0      # MPOPIS_RISK_TAIL_MEAN
+const RISK_ENTROPIC = 1       # MPOPIS_RISK_ENTROPIC
+function set_scenarios!(pol::AbstractPathIntegralPolicy, env, P::AbstractMatrix{<:Real})
+    h = handle(pol, env)
+    Pm = Matrix{Float64}(P)
+    M = size(Pm, 2)
+    GC.@preserve Pm check(h, ccall((:mpopis_set_scenarios, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Int32),
+                                   h, Int32(M), M == 0 ? C_NULL : pointer(Pm), Int32(size(Pm, 1)), Int32(0)))
+    pol
+end
+function set_risk!(pol::AbstractPathIntegralPolicy, env, kind::Symbol; tail::Integer = 0, θ::Real = 0.0)
+    h = handle(pol, env)
+    kind in (:mean, :worst, :cvar, :entropic) || error("set_risk!: :mean, :worst, :cvar or :entropic")
+    k = kind == :entropic ? RISK_ENTROPIC : RISK_TAIL_MEAN
+    t = kind == :worst ? 1 : kind == :cvar ? tail : 0
+    check(h, ccall((:mpopis_set_risk, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Float64), h, Int32(k), Int32(t), Float64(θ)))
+    pol
+end
+
 end # module

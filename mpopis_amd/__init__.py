@@ -11,7 +11,7 @@ from .envs import (CarRacingEnv, CarRacingEnvParams, MultiCarRacingEnv, Mountain
 from .policies import (MPPI_Policy, GMPPI_Policy, IMPPI_Policy, CEMPPI_Policy, CMAMPPI_Policy, μAISMPPI_Policy,  # noqa: F401
                        μΣAISMPPI_Policy, PMCMPPI_Policy, NESMPPI_Policy, muAISMPPI_Policy, muSigmaAISMPPI_Policy, get_policy,
                        calculate_trajectory_costs, simulate_model, AbstractGMPPI_Policy, AbstractPathIntegralPolicy)
-from .examples import simulate_car_racing, simulate_mountaincar, simulate_cartpole, quantile_ci, shard_trials, split_tracks_per_trial, split_env_params_per_trial  # noqa: F401
+from .examples import simulate_car_racing, simulate_mountaincar, simulate_cartpole, quantile_ci, shard_trials, split_tracks_per_trial, split_env_params_per_trial, split_model_params_per_trial  # noqa: F401
 
 
 def block_diagm(A, rep_number):

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "mpopis_set_slot_hyper", "mpopis_get_slot_hyper", "mpopis_set_Sigma_slots", "mpopis_set_env_params_slots", "mpopis_set_tracks",
     "mpopis_get_plan", "mpopis_run_trials_traced", "mpopis_set_env_params_cars",
     "mpopis_set_noise_kind", "mpopis_get_noise_kind", "mpopis_draw_normals",
+    "mpopis_set_scenarios", "mpopis_set_risk", "mpopis_get_scenarios", "mpopis_get_scenario_costs",
 ]
 # MPOPIS_NOISE_*: how the device draws the proposal's standard normals (mpopis_set_noise_kind)
 NOISE_IDS = {"philox": 0, "antithetic": 1, "lhs": 2}
@@ -113,6 +114,11 @@ def lib():
             L.mpopis_set_noise_kind.argtypes = [H, C.c_int32]
             L.mpopis_get_noise_kind.argtypes = [H, _ip]
             L.mpopis_draw_normals.argtypes = [H, C.c_uint32, C.c_int32, _dp]
+        if hasattr(L, "mpopis_set_scenarios"):                  # (scenario rollouts and risk costs)
+            L.mpopis_set_scenarios.argtypes = [H, C.c_int32, _dp, C.c_int32, C.c_int32]
+            L.mpopis_set_risk.argtypes = [H, C.c_int32, C.c_int32, C.c_double]
+            L.mpopis_get_scenarios.argtypes = [H, _ip, _ip, _ip, _dp]
+            L.mpopis_get_scenario_costs.argtypes = [H, _dp]
         L.mpopis_destroy.argtypes = [H]
         L.mpopis_destroy.restype = None
         L.mpopis_set_env_params.argtypes = [H, _dp, C.c_int32]

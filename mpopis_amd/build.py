@@ -11,7 +11,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmpopis_hip.so")
 SOURCES = ["engine_api.hip", "engine_ais.hip", "engine_harness.hip", "engine_comm.hip", "kernels_rollout.hip", "kernels_rollout_slots.hip", "kernels_rollout_fleet.hip", "kernels_reweight.hip",
            "kernels_sample.hip", "kernels_strat.hip", "kernels_linalg.hip", "kernels_select.hip", "kernels_ce.hip", "kernels_cma.hip", "kernels_invsqrt.hip", "kernels_mfma.hip",
-           "kernels_nes.hip", "kernels_plan.hip", "kernels_trace.hip", "kernels_harness.hip"]
+           "kernels_nes.hip", "kernels_plan.hip", "kernels_trace.hip", "kernels_harness.hip", "kernels_risk.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 ENV_FLAGS = ["--genco", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", "-I", INCLUDE]      # the library's own optimisation flags

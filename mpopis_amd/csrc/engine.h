@@ -188,6 +188,11 @@ RolloutForm rollout_form(const RolloutArgs& a);
 constexpr size_t fleet_static_lds(int ncars) { return (size_t)ncars * (2 * 2 * 64 + 4) * sizeof(double); }
 bool launch_car_rollout_fleet(const RolloutArgs& a, const RolloutForm& f, hipStream_t st);
 bool launch_rollout(const RolloutArgs& a, hipStream_t s, hipError_t* custom_err = nullptr);      // false: nothing launched -- no rollout kernel for this env, or the custom env's launch failed (*custom_err says why)
+// kernels_risk.hip (scenario handles): cost[b][k] = the risk aggregate (MPOPIS_RISK_*: kind, tail in 1..M, theta) of the M
+// scenario costs sc[m * pstride + b * K + k]; slots with active == 0 are skipped; cmin / status (nullable) as in the rollout's epilogue.
+// false: no kernel for this M (outside 1..MPOPIS_MAX_SCENARIOS)
+bool launch_risk(const double* sc, size_t pstride, int M, double* cost, int B, int K, int kind, int tail, double theta, const int* active,
+                 unsigned long long* cmin, int* status, hipStream_t s);
 void launch_extend_state(const double* x, double* xext, int B, int ncars, hipStream_t s, const Track& tk, const Track* slot_tk = nullptr /* [B], or null: tk in every slot */);
 // (iters_acc: per-slot running sum of the iteration counts of earlier steps, folded in before iters is cleared; may be null)
 void launch_step_begin(int* status, int* active, const int* alive, int* iters, const double* U, double* Uin, double* Ucur, int B, int cs,

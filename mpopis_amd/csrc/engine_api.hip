@@ -482,7 +482,9 @@ int mpopis_set_env_params(mpopis_handle* h, const double* p, int32_t n) {
 // Car handles: while exactly one of the per-slot arrays is in force, fill the other with B copies of the shared value (engine_handle.h).  The caller
 // has quiesced the handle.  (A shared track that is not set yet gives descriptors with P = 0: track_missing() then refuses the calls that need one.)
 int mpopis_handle::sync_slot_env() {
-    if (env.kind != MPOPIS_ENV_CAR || (env_params_slots_on || fleet_on) == track_slots_on) return MPOPIS_OK;
+    if (env.kind != MPOPIS_ENV_CAR) return MPOPIS_OK;
+    const bool params_on = env_params_slots_on || fleet_on;
+    if (track_slots_on ? params_on : !(params_on || scen_M > 0)) return MPOPIS_OK;      // (a scenario handle's rollouts read the track array too)
     const char* msg = "hipMalloc of the per-slot env arrays failed";
     if (track_slots_on) {
         if (slot_alloc(d_car_sl, 1)) { (void)hipGetLastError(); err = msg; return MPOPIS_ERR_HIP; }
@@ -543,6 +545,7 @@ int mpopis_set_env_params_cars(mpopis_handle* h, const double* p, int32_t n, int
     if (!p) { h->err = "mpopis_set_env_params_cars: p is NULL"; return MPOPIS_ERR_ARG; }
     if (h->env.kind == MPOPIS_ENV_CUSTOM) { h->err = "mpopis_set_env_params_cars: not for a custom handle (a custom env has no cars)"; return MPOPIS_ERR_ARG; }
     if (h->env.kind != MPOPIS_ENV_CAR) { h->err = "mpopis_set_env_params_cars: not a car handle (only MultiCarRacingEnv holds several cars)"; return MPOPIS_ERR_ARG; }
+    if (h->scen_M > 0) { h->err = "mpopis_set_env_params_cars: not on a scenario handle (all cars of a slot share the scenario's vector; end the mode with mpopis_set_scenarios(h, 0, ...) first)"; return MPOPIS_ERR_ARG; }
     if (n != MPOPIS_CAR_NPARAMS) { h->err = "mpopis_set_env_params_cars: a car expects 20 parameters, got n = " + std::to_string(n); return MPOPIS_ERR_ARG; }
     const int B = h->B_full, NC = h->env.ncars;
     if (NC == 1) return per_slot ? mpopis_set_env_params_slots(h, p, n) : mpopis_set_env_params(h, p, n);      // one car: the existing forms and kernels
@@ -567,6 +570,101 @@ int mpopis_set_env_params_cars(mpopis_handle* h, const double* p, int32_t n, int
     const int rc = h->sync_slot_env();
     if (rc) { h->env_params_slots_on = was; h->fleet_on = was_fleet; }
     return rc;
+}
+
+// M model parameter vectors per slot for the rollouts of a policy step.  A setup call like mpopis_set_env_params_slots:
+// everything is checked and formed on the host first, new buffers (first call, or M beyond what is allocated) are all allocated before the handle
+// changes, and the struct planes are written only after everything queued has finished.
+int mpopis_set_scenarios(mpopis_handle* h, int32_t M, const double* p, int32_t n, int32_t per_slot) {
+    if (h) h->plan_drop("mpopis_set_scenarios");
+    if (!h) return MPOPIS_ERR_ARG;
+    const int kind = h->env.kind, B = h->B_full;
+    if (M < 0 || M > MPOPIS_MAX_SCENARIOS) { h->err = "mpopis_set_scenarios: M must be 0.." + std::to_string(MPOPIS_MAX_SCENARIOS) + ", got " + std::to_string(M); return MPOPIS_ERR_ARG; }
+    if (kind == MPOPIS_ENV_CUSTOM) { h->err = "mpopis_set_scenarios: not for a custom handle (its parameters belong to the caller's code object)"; return MPOPIS_ERR_ARG; }
+    if (M == 0) {
+        if (h->scen_M == 0) return MPOPIS_OK;
+        if (const int rc = quiesce(h)) return rc;
+        h->scen_M = 0; h->risk_kind = MPOPIS_RISK_TAIL_MEAN; h->risk_tail = 0; h->risk_theta = 0.0;
+        return MPOPIS_OK;
+    }
+    if (!p) { h->err = "mpopis_set_scenarios: p is NULL with M > 0"; return MPOPIS_ERR_ARG; }
+    const int want = kind == MPOPIS_ENV_CAR ? MPOPIS_CAR_NPARAMS : kind == MPOPIS_ENV_CARTPOLE ? MPOPIS_CARTPOLE_NPARAMS : MPOPIS_MOUNTAINCAR_NPARAMS;
+    if (n != want) {
+        h->err = "mpopis_set_scenarios: this env expects " + std::to_string(want) + " parameters per scenario, got n = " + std::to_string(n);
+        return MPOPIS_ERR_ARG;
+    }
+    if (h->d_traj) { h->err = "mpopis_set_scenarios: not on a handle created with log_trajectories (the logger holds one trajectory per sample, a scenario step rolls M)"; return MPOPIS_ERR_ARG; }
+    if (h->fleet_on) { h->err = "mpopis_set_scenarios: not on a fleet handle (mpopis_set_env_params_cars in force; all cars of a slot share the scenario's vector)"; return MPOPIS_ERR_ARG; }
+    if (const int rc = quiesce(h)) return rc;
+    const char* nomem = "mpopis_set_scenarios: hipMalloc of the scenario buffers failed";
+    const size_t planes = (size_t)std::max(M, h->scen_cap);
+    auto upload = [&](auto*& dst, auto make) -> int {
+        using P = std::remove_reference_t<decltype(*dst)>;
+        std::vector<P> host((size_t)M * B);
+        for (int m = 0; m < M; ++m)
+            for (int b = 0; b < B; ++b) host[(size_t)m * B + b] = make(p + ((size_t)(per_slot ? b : 0) * M + m) * n);
+        P* par = dst; double* cost = h->d_scen_cost;
+        if (M > h->scen_cap) {                                 // both allocated before either replaces what the handle holds
+            void *q = nullptr, *c = nullptr;
+            if (h->dev_alloc(&q, planes * B * sizeof(P)) || h->dev_alloc(&c, planes * B * h->K * sizeof(double))) { (void)hipGetLastError(); h->err = nomem; return MPOPIS_ERR_HIP; }
+            par = (P*)q; cost = (double*)c;
+        }
+        HIPCHK(h, hipMemcpyAsync(par, host.data(), sizeof(P) * host.size(), hipMemcpyHostToDevice, h->stream));      // (behind the buffer's zero-fill)
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (!h->scen_cap) { h->slot_view(dst, 1); h->slot_view(h->d_scen_cost, (size_t)h->K); }      // (registered once: the members keep their addresses)
+        dst = par; h->d_scen_cost = cost; h->scen_cap = (int)planes;
+        return MPOPIS_OK;
+    };
+    int rc;
+    if (kind == MPOPIS_ENV_CAR) rc = upload(h->d_scen_car, [](const double* q) { return make_car_params(q); });
+    else if (kind == MPOPIS_ENV_CARTPOLE) rc = upload(h->d_scen_cp, [](const double* q) { return make_cp_params(q); });
+    else rc = upload(h->d_scen_mc, [](const double* q) { return make_mc_params(q); });
+    if (rc) return rc;
+    const int was = h->scen_M;
+    h->scen_M = M;
+    if ((rc = h->sync_slot_env())) { h->scen_M = was; return rc; }
+    h->risk_kind = MPOPIS_RISK_TAIL_MEAN; h->risk_tail = M; h->risk_theta = 0.0;
+    return MPOPIS_OK;
+}
+
+int mpopis_set_risk(mpopis_handle* h, int32_t kind, int32_t tail, double theta) {
+    if (h) h->plan_drop("mpopis_set_risk");
+    if (!h) return MPOPIS_ERR_ARG;
+    const int M = h->scen_M;
+    if (M == 0) { h->err = "mpopis_set_risk: no scenarios set (mpopis_set_scenarios first)"; return MPOPIS_ERR_ARG; }
+    if (kind == MPOPIS_RISK_TAIL_MEAN) {
+        if (tail < 0 || tail > M) { h->err = "mpopis_set_risk: tail must be 0.." + std::to_string(M) + " (0 = all), got " + std::to_string(tail); return MPOPIS_ERR_ARG; }
+    } else if (kind == MPOPIS_RISK_ENTROPIC) {
+        if (!(theta != 0.0) || !(std::fabs(theta) < INFINITY)) { h->err = "mpopis_set_risk: theta must be finite and non-zero"; return MPOPIS_ERR_ARG; }
+    } else { h->err = "mpopis_set_risk: unknown kind " + std::to_string(kind); return MPOPIS_ERR_ARG; }
+    if (const int rc = quiesce(h)) return rc;
+    h->risk_kind = kind;
+    h->risk_tail = kind == MPOPIS_RISK_TAIL_MEAN ? (tail ? tail : M) : M;
+    h->risk_theta = kind == MPOPIS_RISK_ENTROPIC ? theta : 0.0;
+    return MPOPIS_OK;
+}
+
+int mpopis_get_scenarios(mpopis_handle* h, int32_t* M, int32_t* kind, int32_t* tail, double* theta) {
+    if (!h) return MPOPIS_ERR_ARG;
+    if (M) *M = h->scen_M;
+    if (kind) *kind = h->risk_kind;
+    if (tail) *tail = h->risk_tail;
+    if (theta) *theta = h->risk_theta;
+    return MPOPIS_OK;
+}
+
+// out[b][m][k] from the planes [m][B_full][K]: one strided copy per scenario
+int mpopis_get_scenario_costs(mpopis_handle* h, double* out) {
+    if (!h) return MPOPIS_ERR_ARG;
+    if (!out) { h->err = "mpopis_get_scenario_costs: out is NULL"; return MPOPIS_ERR_ARG; }
+    if (h->scen_M == 0) { h->err = "mpopis_get_scenario_costs: no scenarios set"; return MPOPIS_ERR_ARG; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t B = (size_t)h->B_full, K = (size_t)h->K, M = (size_t)h->scen_M;
+    for (size_t m = 0; m < M; ++m)
+        HIPCHK(h, hipMemcpy2DAsync(out + m * K, sizeof(double) * M * K, h->d_scen_cost + m * B * K, sizeof(double) * K, sizeof(double) * K, B,
+                                   hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, wait_stream(h->stream));
+    return MPOPIS_OK;
 }
 
 // The table of a caller's env (MPOPIS_DEFINE_ENV_TABLE).  A setup call: it waits for everything the handle has queued, on the part-chain streams
@@ -616,7 +714,7 @@ int mpopis_set_track(mpopis_handle* h, const double* x, const double* y, const d
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Track tk;
     if (const int rc = upload_track(h, x, y, w, P, &tk)) return rc;
-    if (h->env_params_slots_on || h->track_slots_on || h->fleet_on) {      // (after mpopis_set_tracks: back to one shared track)
+    if (h->env_params_slots_on || h->track_slots_on || h->fleet_on || h->scen_M > 0) {      // (after mpopis_set_tracks: back to one shared track)
         if (const int rc = quiesce(h)) return rc;
         h->env.track = tk;
         h->track_slots_on = false;
@@ -1339,7 +1437,7 @@ RolloutArgs mpopis_handle::rollout_base() const {
     a.x0 = d_x; a.x0ext = d_xext; a.t0 = d_t; a.done0 = d_done;
     a.Ucur = a.Uorig = a.E = a.gvec = nullptr; a.cost = a.traj = nullptr;
     a.active = nullptr; a.iters = nullptr; a.iter_n = 0; a.cmin = nullptr; a.status = nullptr;
-    a.senv = slot_env();
+    a.senv = scen_M > 0 ? scenario_env(0) : slot_env();      // (scenario 0 = the nominal model: what the plan read-outs roll under)
     return a;
 }
 
@@ -1360,6 +1458,22 @@ void mpopis_handle::rollout(const double* Ucur, const double* Uorig, const doubl
     a.share = coop_share;
     time_begin(0);
     hipError_t custom_err = hipSuccess;
+    if (scen_M > 0) {
+        // One launch of the per-slot form per scenario, serial on the part's stream, each into its own cost plane and none of them touching
+        // cmin / status; then the risk kernel forms the K costs the step sees and does the epilogue's cmin / status work on those.
+        unsigned long long* cmin = a.cmin; int* status = a.status;
+        a.cmin = nullptr; a.status = nullptr; a.traj = nullptr;
+        const size_t plane = (size_t)B_full * K;
+        bool ok = true;
+        for (int m = 0; m < scen_M && ok; ++m) {
+            a.senv = scenario_env(m); a.cost = d_scen_cost + m * plane;
+            ok = launch_rollout(a, stream, &custom_err);
+        }
+        ok = ok && launch_risk(d_scen_cost, plane, scen_M, d_cost, B, K, risk_kind, risk_tail, risk_theta, act, cmin, status, stream);
+        if (!ok && launch_err.empty()) launch_err = "rollout: no kernel for this env under scenarios (num_cars " + std::to_string(env.ncars) + ")";
+        time_end();
+        return;
+    }
     if (!launch_rollout(a, stream, &custom_err) && launch_err.empty())
         launch_err = env.kind == MPOPIS_ENV_CUSTOM ? std::string("rollout: launching the custom env's kernel failed: ") + hipGetErrorString(custom_err)
                                                    : "rollout: no kernel for this env (num_cars " + std::to_string(env.ncars) + ")";

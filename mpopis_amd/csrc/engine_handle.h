@@ -103,6 +103,25 @@ struct mpopis_handle {
         return se;
     }
     const mpopis::Track* slot_tracks() const { return slot_env().track; }
+    // Scenarios (mpopis_set_scenarios): scen_M > 0 model parameter vectors per slot that the ROLLOUTS of a policy step run
+    // under, one launch of the per-slot form each; the real env keeps slot_env().  Layout [scen_cap][B_full] ready-made structs of the handle's env
+    // kind and [scen_cap][B_full][K] costs: scenario m is the plane m * B_full slots behind the pointer, which is that of the handle's first slot in
+    // plane 0 and moves with the slot views like any [B_full][...] buffer -- so a launch addresses its plane exactly as a plain launch addresses
+    // d_car_sl / d_cost.  scen_cap: planes allocated (grows with M; the old buffers stay owned until mpopis_destroy).  On a car handle d_track_sl is
+    // kept valid while the mode is on (sync_slot_env fills it with copies of the shared descriptor when no per-slot tracks are set).
+    int scen_M = 0, scen_cap = 0, risk_kind = MPOPIS_RISK_TAIL_MEAN, risk_tail = 0;
+    double risk_theta = 0.0;
+    mpopis::CarParams* d_scen_car = nullptr; mpopis::McParams* d_scen_mc = nullptr; mpopis::CpParams* d_scen_cp = nullptr;
+    double* d_scen_cost = nullptr;
+    mpopis::SlotEnv scenario_env(int m) const {                // what the rollouts of scenario m read: its parameters, the handle's tracks
+        mpopis::SlotEnv se;
+        const size_t o = (size_t)m * B_full;
+        if (d_scen_car) se.car = d_scen_car + o;
+        if (d_scen_mc) se.mc = d_scen_mc + o;
+        if (d_scen_cp) se.cp = d_scen_cp + o;
+        if (env.kind == MPOPIS_ENV_CAR) { se.track = d_track_sl; se.lds_all = track_sl_lds_all; se.lds_ring = track_sl_lds_ring; }
+        return se;
+    }
     int sync_slot_env();                                       // engine_api.hip; sets err
     bool fold_weights_cfg = false;                // what weights_in_moments is while λ_ais is the config's scalar
     // samples / costs / weights

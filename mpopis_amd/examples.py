@@ -10,6 +10,7 @@ import numpy as np
 
 from .engine import Engine, default_track
 from ._lib import MPOPISError, ERR_ARG, RECORD_LEN, noise_id
+from .scenarios import parse_risk
 
 
 def quantile_ci(x, p=0.05, q=0.5):
@@ -140,6 +141,28 @@ def split_env_params_per_trial(value, n, num_trials, rank=0, world=1):
     return None, a[[k - 1 for k in shard_trials(num_trials, rank, world)]]
 
 
+def split_model_params_per_trial(value, n, num_trials, rank=0, world=1):
+    """What one rank passes for `model_params` to Engine.set_scenarios, as (params, per_slot) (None, False: no scenarios): (M, n) as it is -- every
+    trial plans against those M models --, or from (num_trials, M, n) the blocks of this rank's trials (shard_trials) in slot order."""
+    if value is None:
+        return None, False
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 2 and a.shape[1] == n and a.shape[0] >= 1:
+        return a, False
+    if a.ndim != 3 or a.shape[0] != num_trials or a.shape[2] != n or a.shape[1] < 1:
+        raise ValueError("model_params: shape (M, %d), or one block per trial (%d, M, %d), got %s" % (n, num_trials, n, a.shape))
+    return a[[k - 1 for k in shard_trials(num_trials, rank, world)]], True
+
+
+def _apply_scenarios(eng, model, per_slot, risk):
+    """Engine.set_scenarios / set_risk from split_model_params_per_trial and the harness's risk= keyword."""
+    if model is None:
+        return
+    eng.set_scenarios(model, per_slot=per_slot)
+    kind, tail, theta = parse_risk(risk)
+    eng.set_risk(kind, tail=tail, theta=theta)
+
+
 def split_fleet_per_trial(value, num_cars, num_trials, rank=0, world=1):
     """What one rank passes for `car_fleet` to Engine.set_env_params_cars (None: no fleet): (num_cars, 20) as it is -- every trial drives that
     fleet --, or from (num_trials, num_cars, 20) the fleets of this rank's trials (shard_trials) in slot order."""
@@ -169,7 +192,8 @@ def _apply_per_trial(eng, per, cov_slots, policy):
 def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="cemppi", laps=2, num_samples=150, horizon=50,
                         λ=10.0, α=1.0, U0=None, cov_mat=None, ais_its=10, λ_ais=20.0, ce_elite_threshold=0.8, ce_Σ_est="ss",
                         cma_σ=0.75, cma_elite_threshold=0.8, state_x_sigma=0.0, state_y_sigma=0.0, state_ψ_sigma=0.0,
-                        seed=None, log_runs=True, device=0, dist=None, quiet=False, track="curve", car_params=None, trace=None, car_fleet=None, noise="philox"):
+                        seed=None, log_runs=True, device=0, dist=None, quiet=False, track="curve", car_params=None, trace=None, car_fleet=None, noise="philox", model_params=None,
+                        risk="mean"):
     """Returns (records, summary) on rank 0 (None elsewhere).  Differences from the reference harness, all
     forced by the platform: plotting/GIF options are not offered (out of scope); the state noise (single car only,
     car_example.jl:224-236) is drawn from the trial's device stream instead of the env's MersenneTwister.
@@ -183,9 +207,13 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
     trace: as Engine.run_trials takes it (True, or dict(plan_every, top[, fields])) -- the run is recorded on the device, what plot_steps /
     save_gif / plot_traj of the reference draw, and the call returns (records, summary, trace) with the trace of THIS rank's trials in slot
     order (trial ids: shard_trials; traces are not gathered; an empty dict on a rank without trials).
-    noise: how every trial draws its proposal's normals -- "philox" (default), "antithetic" or "lhs" (Engine.set_noise_kind); one kind per call."""
+    noise: how every trial draws its proposal's normals -- "philox" (default), "antithetic" or "lhs" (Engine.set_noise_kind); one kind per call.
+    model_params: plan against M car models at once (Engine.set_scenarios) -- (M, 20) for every trial, or (num_trials, M, 20), sharded like
+    car_params (split_model_params_per_trial) -- while the car that is driven keeps car_params; risk: how a sample's M costs become its cost,
+    "mean", "worst", ("cvar", tail) or ("entropic", θ) (Engine.set_risk).  Not together with car_fleet."""
     pt = str(policy_type).lstrip(":")
     noise_id(noise)                                    # (an unknown kind is refused before the library is reached)
+    parse_risk(risk)
     rank = dist.get_rank() if (dist is not None and dist.is_initialized()) else 0
     world = dist.get_world_size() if (dist is not None and dist.is_initialized()) else 1
     if seed is None:
@@ -207,6 +235,9 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
         raise ValueError("car_params and car_fleet: give one of the two (one vector per slot, or one per car)")
     par_shared, par_slots = split_env_params_per_trial(car_params, 20, num_trials, rank, world)
     fleet = split_fleet_per_trial(car_fleet, num_cars, num_trials, rank, world)
+    if model_params is not None and car_fleet is not None:
+        raise ValueError("model_params and car_fleet: scenarios give all cars of a slot one vector, a fleet one per car")
+    model, model_per_slot = split_model_params_per_trial(model_params, 20, num_trials, rank, world)
     t0 = time.time()
     # every rank keeps a handle (even with no trials: it takes part in the collective); all of a rank's trials
     # k0, k0+G, ... live in ONE resident batch, slot i seeded like the reference's trial k_i: seed!(pol, seed + k) (:187-188)
@@ -225,6 +256,7 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
             eng.set_env_params_slots(par_slots)
         if fleet is not None:
             eng.set_env_params_cars(fleet)
+        _apply_scenarios(eng, model, model_per_slot, risk)
         eng.seed_slots([seed + k for k in mine])
         if noise_id(noise) != 0:
             eng.set_noise_kind(noise)
@@ -271,9 +303,12 @@ def simulate_car_racing(num_trials=1, num_steps=200, num_cars=1, policy_type="ce
 
 def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cemppi", num_samples=20, horizon=15, λ=0.1, α=1.0, U0=(0.0,),
                          cov_mat=(1.5,), ais_its=5, λ_ais=0.1, ce_elite_threshold=0.8, ce_Σ_est="mle", cma_σ=0.75,
-                         cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None, noise="philox"):
+                         cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None, noise="philox",
+                         model_params=None, risk="mean"):
     pt = str(policy_type).lstrip(":")
     noise_id(noise)                                    # (an unknown kind is refused before the library is reached)
+    parse_risk(risk)
+    model, model_per_slot = split_model_params_per_trial(model_params, 11 if env_kind == "cartpole" else 8, num_trials)
     par_shared, par_slots = split_env_params_per_trial(env_params, 11 if env_kind == "cartpole" else 8, num_trials)
     if seed is None:
         seed = int(np.random.default_rng().integers(1, 10 ** 10))
@@ -288,6 +323,7 @@ def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cem
     _apply_per_trial(eng, {k: v[1] for k, v in split.items()}, cov_slots, pt)
     if par_slots is not None:
         eng.set_env_params_slots(par_slots)
+    _apply_scenarios(eng, model, model_per_slot, risk)
     if x0 is not None:
         eng.set_state(np.asarray(x0, dtype=np.float64).reshape(num_trials, ss))
     if noise_id(noise) != 0:
@@ -311,14 +347,16 @@ def _simulate_simple(env_kind, ss, num_trials=1, num_steps=200, policy_type="cem
 
 _SIMPLE_KW = dict(num_trials=1, num_steps=200, policy_type="cemppi", num_samples=20, horizon=15, λ=0.1, α=1.0, U0=(0.0,),
                   cov_mat=(1.5,), ais_its=5, λ_ais=0.1, ce_elite_threshold=0.8, ce_Σ_est="mle", cma_σ=0.75,
-                  cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None, noise="philox")
+                  cma_elite_threshold=0.8, seed=None, x0=None, log_runs=True, device=0, quiet=False, env_params=None, trace=None, noise="philox",
+                  model_params=None, risk="mean")
 
 
 def simulate_mountaincar(**kw):
     """mountaincar_example.jl:49-207 (same keyword arguments and defaults); x0: per-trial start positions
     (the reference draws x ~ U(-0.6,-0.4) from an unseeded RNG; default here -0.5).  env_params: the 8 values include/mpopis.h lists for
     MountainCar, or (num_trials, 8) for one vector per trial.  trace: as simulate_car_racing; the call then returns (records, summary, trace).
-    noise: "philox" (default), "antithetic" or "lhs", as simulate_car_racing."""
+    noise: "philox" (default), "antithetic" or "lhs", as simulate_car_racing.  model_params ((M, 8) or (num_trials, M, 8)) / risk: plan against M
+    models while env_params stays the plant, as simulate_car_racing."""
     a = dict(_SIMPLE_KW); _check_kw(a, kw); a.update(kw)
     if a["x0"] is not None:
         x = np.asarray(a["x0"], dtype=np.float64).reshape(a["num_trials"])
@@ -331,7 +369,8 @@ def simulate_cartpole(**kw):
     [x, xdot, theta, thetadot].  The reference draws 0.1*rand(4) - 0.05 from an unseeded MersenneTwister (:111);
     default here: the same box drawn from numpy's default_rng(seed + k).  env_params: the 11 values include/mpopis.h lists for CartPole, or
     (num_trials, 11) for one vector per trial.  trace: as simulate_car_racing; the call then returns (records, summary, trace).
-    noise: "philox" (default), "antithetic" or "lhs", as simulate_car_racing."""
+    noise: "philox" (default), "antithetic" or "lhs", as simulate_car_racing.  model_params ((M, 11) or (num_trials, M, 11)) / risk: plan against M
+    models while env_params stays the plant, as simulate_car_racing."""
     a = dict(_SIMPLE_KW); _check_kw(a, kw); a.update(kw)
     if a["seed"] is None:
         a["seed"] = int(np.random.default_rng().integers(1, 10 ** 10))

@@ -83,6 +83,16 @@ class AbstractPathIntegralPolicy:
     def noise_kind(self, kind):
         self._eng.set_noise_kind(kind)
 
+    def set_scenarios(self, params):
+        """Plan against M model parameter vectors at once: params (M, n), n as env's parameter vector; pol(env) then scores every sample under
+        each and weighs it by the risk aggregate of set_risk ("mean" after this call).  The env the caller steps is not touched: M = 1 plans
+        with a model that differs from the plant.  None ends it.  Not with log=True (Engine.set_scenarios)."""
+        self._eng.set_scenarios(None if params is None else np.asarray(params, dtype=np.float64))
+
+    def set_risk(self, kind, tail=0, theta=0.0):
+        """ "mean" | "worst" | "cvar" (tail) | "entropic" (theta) over the scenario costs (Engine.set_risk)."""
+        self._eng.set_risk(kind, tail=tail, theta=theta)
+
     def seed(self, seed):
         """Random.seed!(pol, seed): src/MPOPIS.jl:54"""
         self._eng.seed(int(seed) - 1)          # slot 0 draws from seed+0+1

@@ -17,7 +17,9 @@ case "$name" in
     # the launchers reach into the rest of the library (launch_ce_cov_general beside the handle in engine_ais.o, coop_max_workgroups, launch_env_step's
     # custom-env branch), so the whole library's objects are linked
     mfma|adapt|dense|rollout|loop) link="$obj/*.o -ldl" ;;
-    *) echo "usage: $0 select|mfma|adapt|dense|dynamics|rollout|sample|strat|loop"; exit 2 ;;
+    # the risk aggregate of a scenario handle: one launcher, one object
+    risk)     link="$obj/kernels_risk.o" ;;
+    *) echo "usage: $0 select|mfma|adapt|dense|dynamics|rollout|sample|strat|loop|risk"; exit 2 ;;
 esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 $flags -Wno-unused-result -c tools/kbench_$name.hip -o tools/kbench_$name.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 tools/kbench_$name.o $link -o tools/kbench_${name}_bin
